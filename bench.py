@@ -23,6 +23,9 @@ crop count / HIP-event time of exactly those launches timed in sequence, vs the 
 (N=1: BASELINE configs[1] detector-only at both network sizes, the 64x64 crop size, configs[4] tiled 4K) and
 `cpu_baseline` (the reference-equivalent CPU path from oracle/, timed on rank 0 at N=1 on a bounded sample).
 Weights are seeded-random (tools/make_weights.py); data is synthetic (omniparser_amd/synth.py).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path returned in its last step as DIR/<name>.npy (float32 /
+float64; see dump_outputs), so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -61,6 +64,8 @@ def parse_args():
     ap.add_argument("--width", type=float, default=1.0, help="debug only: detector channel multiplier (1.0 = YOLOv9-E)")
     ap.add_argument("--frame", default="1920x1080", help="debug only: synthetic frame size WxH (the metric is quoted on 1920x1080; the CPU test "
                     "of the N > 1 path runs a small frame on the host emulation)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (rank 0) as DIR/<name>.npy (float32 / float64)")
     a = ap.parse_args()
     if a.batch is None:
         a.batch = 8 if a.mode == "e2e" else 1
@@ -98,7 +103,6 @@ def main():
     from omniparser_amd import dist as OD
     from omniparser_amd.synth import BENCH_SEEDS, synthetic_ocr, synthetic_screenshot
     from omniparser_amd.util.yolov9 import YOLOv9Detector
-    from tools.make_weights import caption_dir, default_path, ensure_via_subprocess   # imports nothing from oracle/
 
     rank, world, local_rank = OD.init_from_env()
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
@@ -106,6 +110,7 @@ def main():
         # N processes share the host: without a cap every rank's CPU-side torch ops (hand-off tables, record packing, tokenizer glue)
         # spawn one worker per core of the whole box and the ranks thrash each other
         torch.set_num_threads(max(1, (os.cpu_count() or world) // world))
+    load_native()
     dev = L.require_device(torch.device("cuda", local_rank), "bench.py")       # the MI355X or nothing (no CPU fallback)
     torch.cuda.set_device(local_rank)
     global IW, IH
@@ -113,13 +118,7 @@ def main():
     imgsz = int(args.imgsz) if args.imgsz.isdigit() else (IH, IW)
     # stand-in checkpoints are INPUT FILES (the reference downloads its weights): generated once, in a separate
     # process, by tools/make_weights.py — this process never imports oracle/ outside cpu_baseline()
-    if rank == 0:
-        ensure_via_subprocess("detector", seed=0, nc=1, width=args.width)
-        if args.mode == "e2e":
-            ensure_via_subprocess("caption", seed=0)
-    if world > 1:
-        dist.barrier()
-    blob = default_path(0, 1, args.width)
+    blob, cap_dir = standin_checkpoints(args, rank, world)
     assert blob.exists(), blob
     note("stand-in checkpoints ready")
     det = YOLOv9Detector(model_path=blob, device=dev, precision=args.precision)
@@ -135,7 +134,7 @@ def main():
     if args.mode == "e2e":
         from omniparser_amd.florence import Florence2Captioner
         from omniparser_amd.pipeline import ScreenParser
-        cap = Florence2Captioner(caption_dir(0), dev, precision=args.precision, resolution=args.caption_res)
+        cap = Florence2Captioner(cap_dir, dev, precision=args.precision, resolution=args.caption_res)
         parser = ScreenParser(det, cap, box_threshold=CONF, iou_threshold=OVERLAP_IOU, nms_iou=NMS_IOU, max_det=MAX_DET, imgsz=imgsz,
                               batch_size=args.micro_batch)
         parser.encode_lanes = args.lanes
@@ -144,6 +143,7 @@ def main():
 
     recs = torch.zeros(args.steps * B, OD.REC_W, dtype=torch.int32, device=dev)
     crop_counts = []
+    last = {}                            # what the timed path returned in its most recent step (e2e: elements + caption ids)
 
     @torch.inference_mode()
     def step(step_id, li=None):
@@ -170,6 +170,7 @@ def main():
     def pack(step_id, li, elems, ids):
         step_done.append(time.perf_counter())
         crop_counts.append(sum(parser.stats["crops"]))
+        last["elems"], last["ids"] = elems, ids
         if li is not None:
             pack_records(recs, B, dev, step_id, li, elems, ids)
 
@@ -226,6 +227,10 @@ def main():
     if gc_mode == "off":
         gc.enable()
     note(f"timed region done: {elapsed:.2f} s for {args.steps} steps (gc {gc_mode}: collections per generation {gc_runs})")
+    if args.dump_outputs and rank == 0:
+        # outside the timed region, before anything else runs on the plans whose output buffers hold the last step's results
+        names = dump_outputs(Path(args.dump_outputs), args, last, dp if args.mode == "detect" else None)
+        note(f"outputs of the last timed step written to {args.dump_outputs}: {names}")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -326,7 +331,7 @@ def main():
         dp_obj = dp if args.mode == "detect" else None
         guarded("roofline", lambda: roofline(args, det, parser, dp_obj, crop_counts, B))
         if world == 1 and not args.no_extra:
-            guarded("extra", lambda: extras(args, det, parser, frames, ocr, dev))
+            guarded("extra", lambda: extras(args, det, parser, frames, ocr, dev, cap_dir))
         if world == 1 and not args.no_extra and not args.no_ab and args.mode == "e2e" and isinstance(out.get("extra"), dict):
             # this process is done with the GPU: give its activation pools back before the children build their own plans
             try:
@@ -368,6 +373,70 @@ def main():
         dist.destroy_process_group()
 
 
+def load_native():
+    """Bind the library build() made.  The benchmark may run in a checkout that was built and then made read-only, and it is also run
+    over earlier trees of the project to compare their outputs with --dump-outputs; the loader of those takes the build lock (a file
+    opened for writing in the tree) even when nothing is stale.  When that open is refused, a library whose stamp matches the sources
+    is bound directly; a stale or missing one is still an error."""
+    from omniparser_amd import _lib as L
+    try:
+        return L.lib()
+    except OSError:
+        from omniparser_amd import build as BD
+        hdrs = list(BD.CSRC.glob("*.h")) + [BD.PKG.parent / "include" / "omni_amd.h"]
+        if not BD.LIB.exists() or BD._stale(BD.LIB, BD.sources() + hdrs):
+            raise
+        import torch  # noqa: F401  (torch's HIP runtime first, as L.lib() does)
+        L._lib = L.bind(BD.LIB)
+        return L._lib
+
+
+# run in a child process: the stand-in checkpoint of one kind under argv[2] (a directory named `weights`).  Setting ROOT also serves a
+# make_weights.py that predates OMNI_WEIGHTS_DIR (earlier trees of the project: their checkpoints live at <ROOT>/weights/...)
+_GENERATE = ("import sys; from pathlib import Path; sys.path.insert(0, sys.argv[1]); import tools.make_weights as M; "
+             "M.ROOT = Path(sys.argv[2]).parent; "
+             "print(M.ensure_blob(0, 1, float(sys.argv[4])) if sys.argv[3] == 'detector' else M.ensure_caption_checkpoint(0))")
+
+
+def standin_checkpoints(args, rank, world):
+    """(detector blob, caption checkpoint dir) of the seeded stand-ins, generated on first use by rank 0 in a child process.  They live
+    in <repo>/weights when that directory already holds them or can be written; in a read-only checkout, in a per-user cache
+    ($XDG_CACHE_HOME or ~/.cache, else the temp directory).  Same seeds and committed calibration: the same weights either way.
+    OMNI_WEIGHTS_DIR is set to the choice for the child processes of this script."""
+    import subprocess
+    import tempfile
+    import tools.make_weights as MW
+    det_rel = Path(*MW.default_path(0, 1, args.width).parts[-3:])        # icon_detect_v3_<tag>/icon_detect_v3/model.pt
+    cap_rel = Path(MW.caption_dir(0).name)
+    kinds = {"detector": det_rel}
+    if args.mode == "e2e":
+        kinds["caption"] = cap_rel / "model.safetensors"
+    wdir = ROOT / "weights"
+    if not (all((wdir / m).exists() for m in kinds.values()) or os.access(wdir if wdir.exists() else ROOT, os.W_OK | os.X_OK)):
+        cache = Path(os.environ.get("XDG_CACHE_HOME") or Path.home() / ".cache") / "omniparser_amd" / "weights"
+        for wdir in (cache, Path(tempfile.gettempdir()) / f"omniparser_amd-{os.getuid()}" / "weights"):
+            try:
+                wdir.mkdir(parents=True, exist_ok=True)
+            except OSError:
+                continue
+            if os.access(wdir, os.W_OK | os.X_OK):
+                break
+        else:
+            raise RuntimeError("no writable directory for the stand-in checkpoints")
+    os.environ["OMNI_WEIGHTS_DIR"] = str(wdir)
+    if rank == 0:
+        for kind, marker in kinds.items():
+            if not (wdir / marker).exists():
+                cmd = [sys.executable, "-c", _GENERATE, str(Path(MW.__file__).resolve().parents[1]), str(wdir), kind, str(args.width)]
+                r = subprocess.run(cmd, capture_output=True, text=True)
+                if r.returncode != 0 or not (wdir / marker).exists():
+                    raise RuntimeError(f"stand-in {kind} generation failed in {wdir}:\n{r.stderr[-2000:]}")
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+    return wdir / det_rel, wdir / cap_rel
+
+
 def pack_records(recs, B, dev, step_id, li, elems, ids):
     """the parsed elements of one step's B screenshots -> rows li*B .. li*B+B-1 of the job's record table (what the all_gather moves):
     boxes in ratio coordinates, caption ids on the rows of the icons that were captioned, in element order.  Same layout as
@@ -395,6 +464,52 @@ def pack_records(recs, B, dev, step_id, li, elems, ids):
                 v = row.numpy() if hasattr(row, "numpy") else np.asarray(row)
                 cap[i, :min(len(v), CT)] = v[:CT]
     recs[li * B:li * B + B].copy_(torch.from_numpy(host), non_blocking=True)
+
+
+def dump_outputs(d, args, last, dp=None):
+    """--dump-outputs: the arrays a caller of the timed path received in the last timed step, one DIR/<name>.npy each, float32 / float64
+    only (integers as float, exact below 2**24), padded to MAX_DET rows per screenshot; `count` says how many rows of each are real.
+    e2e: the parsed elements of the B screenshots (ratio xyxy boxes, source kind, interactivity, caption ids with -1 padding);
+    detect: the detector's kept boxes (pixels), scores and classes.  A few hundred KB at the default sizes."""
+    import numpy as np
+    from omniparser_amd import dist as OD
+    MD, CT, B = OD.MAX_DET, OD.CAP_TOK, args.batch
+    d.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    if dp is not None:
+        cnt = dp.out_count[:B].cpu().numpy()
+        real = np.arange(MD)[None, :] < cnt[:, None]           # rows past the count are scratch of the plan: written as 0
+        arrs["count"] = cnt.astype(np.float64)
+        arrs["boxes"] = np.where(real[..., None], dp.out_boxes[:B].cpu().numpy(), 0).astype(np.float32)
+        arrs["scores"] = np.where(real, dp.out_scores[:B].cpu().numpy(), 0).astype(np.float32)
+        arrs["cls"] = np.where(real, dp.out_cls[:B].cpu().numpy(), 0).astype(np.float32)
+    else:
+        elems, ids = last["elems"], last["ids"]
+        kinds = {"box_ocr_content_ocr": 0, "box_yolo_content_ocr": 1, "box_yolo_content_yolo": 2}
+        count = np.zeros(B, dtype=np.float64)
+        boxes = np.zeros((B, MD, 4), dtype=np.float64)
+        source = np.full((B, MD), -1.0, dtype=np.float32)
+        interactive = np.zeros((B, MD), dtype=np.float32)
+        caption_ids = np.full((B, MD, CT), -1.0, dtype=np.float32)
+        for j in range(B):
+            el = elems[j][:MD]
+            count[j] = len(el)
+            for i, e in enumerate(el):
+                boxes[j, i] = np.asarray(e["bbox"], dtype=np.float64)
+                source[j, i] = kinds[e["source"]]
+                interactive[j, i] = float(bool(e["interactivity"]))
+            # caption ids belong to the captioned icons, in element order (the pairing pack_records uses)
+            ic = [i for i, e in enumerate(elems[j]) if e["source"] == "box_yolo_content_yolo"][:len(ids[j])]
+            for row, i in zip(ids[j], ic):
+                if i < MD:
+                    v = np.asarray(row.numpy() if hasattr(row, "numpy") else row).reshape(-1)[:CT]
+                    caption_ids[j, i, :len(v)] = v
+        arrs.update(count=count, boxes=boxes, source=source, interactive=interactive, caption_ids=caption_ids)
+    total = sum(a.nbytes for a in arrs.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes exceeds 64 MB"
+    for k, a in arrs.items():
+        np.save(d / f"{k}.npy", a)
+    return sorted(arrs)
 
 
 def child_json(cmd, env, limit_s, keep=None):
@@ -598,14 +713,13 @@ def torch_stream(stream):
     return torch.cuda.stream(stream)
 
 
-def extras(args, det, parser, frames, ocr, dev):
+def extras(args, det, parser, frames, ocr, dev, cap_dir):
     """BASELINE configs[1], the 64x64 (reference cuda-branch) crop size, configs[4] — small runs beside the headline line.
     `value` of the JSON line stays configs[2] at 768x768."""
     import torch
     from omniparser_amd.florence import Florence2Captioner
     from omniparser_amd.pipeline import ScreenParser
     from omniparser_amd.synth import synthetic_ocr, synthetic_screenshot
-    from tools.make_weights import caption_dir
     ex = {}
 
     def time_region(fn, iters, warm=1):
@@ -662,7 +776,7 @@ def extras(args, det, parser, frames, ocr, dev):
                                             "(49.8 MB per step) inside the loop"}
     del host
     # the reference's cuda branch feeds 64x64 crops (ref:util/utils.py:120-121): same pipeline at that crop size
-    cap64 = Florence2Captioner(caption_dir(0), dev, precision=args.precision, resolution=64)
+    cap64 = Florence2Captioner(cap_dir, dev, precision=args.precision, resolution=64)
     p64 = ScreenParser(det, cap64, box_threshold=CONF, iou_threshold=OVERLAP_IOU, nms_iou=NMS_IOU, max_det=MAX_DET, imgsz=640)
     sec = time_region(lambda: p64.parse_batch(frames, ocr), 3)
     ex["e2e_r64_batch8"] = {"value": round(8 / sec, 2), "unit": "screenshots/s", "ms_per_step": round(1000 * sec, 2),

@@ -125,13 +125,17 @@ def ensure_built() -> Path:
     """Return the library path; with hipcc present the library is rebuilt when the CONTENT of any source differs from what the
     shipped objects were compiled from (sha256 stamps next to the objects and the library, which travel with them) and a failing
     compile RAISES (a stale .so must never run in place of the sources the tests were written against).  Without hipcc a library
-    whose stamp does not match the sources is refused as well."""
+    whose stamp does not match the sources is refused as well.  An up-to-date library is returned without taking the build lock, so
+    that a checkout built once and then made read-only loads it."""
+    hdrs = list(CSRC.glob("*.h")) + [PKG.parent / "include" / "omni_amd.h"]
+    srcs = sources()
+    if LIB.exists() and not _stale(LIB, srcs + hdrs) and not any(_stale(OBJ / (s.stem + ".o"), [s] + hdrs) for s in srcs):
+        return LIB
     if os.path.exists(HIPCC):
         return build_lib(verbose=False)
     if not LIB.exists():
         raise RuntimeError(f"{LIB} is missing and hipcc is unavailable: run python -m omniparser_amd.build")
-    hdrs = list(CSRC.glob("*.h")) + [PKG.parent / "include" / "omni_amd.h"]
-    if _stale(LIB, sources() + hdrs):
+    if _stale(LIB, srcs + hdrs):
         raise RuntimeError(f"{LIB} was not built from the sources in this tree and hipcc is unavailable")
     return LIB
 

@@ -73,9 +73,15 @@ def make_blob(path, seed=0, nc=1, width=1.0):
     return model
 
 
+def weights_dir() -> Path:
+    """where the stand-in checkpoints live: <repo>/weights, or $OMNI_WEIGHTS_DIR (bench.py points it at a per-user cache when the
+    checkout is read-only, and its child processes inherit it)"""
+    return Path(os.environ.get("OMNI_WEIGHTS_DIR") or ROOT / "weights")
+
+
 def default_path(seed=0, nc=1, width=1.0):
     tag = f"{DETECTOR_STANDIN}_s{seed}_nc{nc}_w{width:g}"
-    return ROOT / "weights" / f"icon_detect_v3_{tag}" / "icon_detect_v3" / "model.pt"
+    return weights_dir() / f"icon_detect_v3_{tag}" / "icon_detect_v3" / "model.pt"
 
 
 def ensure_blob(seed=0, nc=1, width=1.0):
@@ -144,7 +150,7 @@ def standin_scale(standin=None):
 
 
 def caption_dir(seed=0, standin=CAPTION_STANDIN):
-    return ROOT / "weights" / f"icon_caption_florence_{standin}_s{seed}"
+    return weights_dir() / f"icon_caption_florence_{standin}_s{seed}"
 
 
 def build_random_captioner(seed=0, init_std=0.06, chan_qk_scale=CHAN_QK_SCALE):
