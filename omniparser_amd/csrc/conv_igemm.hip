@@ -641,7 +641,9 @@ void launch_split_cfg(ConvArgs& a, hipStream_t s) {
   a.xcd_order = (a.mtiles >= 64 && a.ntiles > 1) ? 1 : 0;
   a.xcd_n = a.xcd_order ? choose_xcd_n(a.ntiles, 4ll * a.Cout * a.K) : 1;      // 4 bytes per (n, k): hi | lo halves
   dim3 grid(tile_grid(a.mtiles, a.ntiles, a.xcd_order, a.xcd_n), 1, a.splits);
-  const bool pw = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo;
+  // row-patch mode (vec_px) never takes the PW loader: that one reads the 8 vectors of a slice as 8 channels of ONE pixel, unchecked,
+  // i.e. up to 7 pixels beyond the input for a 1 x 1 patch (0-weight taps x whatever lies there, NaN included)
+  const bool pw = !a.vec_px && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo;
   // 128x128: 8 waves (64x32 per wave, 4 waves/SIMD; measured 191-229 TF/s vs 172-209 for 4 waves of 64x64); smaller
   // tiles: 4 waves.  Round-1 variants that lost (two-slice register prefetch, weights straight to registers, 256x128,
   // 64-wide K slices, weight-only LDS-DMA) are recorded in DESIGN.md and profiles/r2_gemm_diag.md, not kept here.

@@ -55,12 +55,14 @@ CONV_CASES = [
 def check_conv_patch(seed=0):
     """PlanBuilder.conv_patch (OMNI_OP_CONV i25: the k x k patch embedding over 4 stored channels as a k x 1 convolution over 8 consecutive
     pixels on the split-f16 kernel) against an f64 convolution and against the exact-f32 kernel it replaces: borders on every side
-    (images smaller than a tile, widths that are no multiple of the stride), NaN in the stored-but-unused 4th channel's NEIGHBOURHOOD is
-    not tested — the 4th channel is data here (its weights are zero only when Cin = 3)."""
+    (images smaller than a tile, widths that are no multiple of the stride), k = 1 / 2 / 7 at stride 1, the input inside NaN guard bands
+    (a 1 x 1 patch once took the pointwise loader, which reads 8 pixels per K slice unchecked).  NaN in the stored-but-unused 4th
+    channel's NEIGHBOURHOOD is not tested — the 4th channel is data here (its weights are zero only when Cin = 3)."""
     g = torch.Generator().manual_seed(seed)
     out = {"cases": 0, "worst_vs_f64": 0.0, "worst_vs_f32_kernel": 0.0}
     for (B, H, W, cin, cout, k, s, p) in ((2, 64, 64, 3, 128, 7, 4, 3), (1, 13, 9, 3, 128, 7, 4, 3), (3, 37, 71, 4, 64, 7, 4, 3),
-                                          (1, 30, 33, 3, 128, 5, 2, 2), (1, 20, 20, 3, 192, 8, 4, 3), (1, 768, 96, 3, 128, 7, 4, 3)):
+                                          (1, 30, 33, 3, 128, 5, 2, 2), (1, 20, 20, 3, 192, 8, 4, 3), (1, 768, 96, 3, 128, 7, 4, 3),
+                                          (2, 9, 13, 4, 64, 1, 1, 0), (1, 11, 7, 4, 64, 2, 1, 0), (1, 10, 9, 3, 128, 7, 1, 3)):
         x = torch.randn(B, 4, H, W, generator=g)
         if cin == 3:
             x[:, 3] = 0.0
@@ -69,12 +71,19 @@ def check_conv_patch(seed=0):
         ref = F.conv2d(x[:, :cin].double(), w.double(), b.double(), stride=s, padding=p)
         Ho, Wo = ref.shape[2:]
         pb = PlanBuilder(DEV, L.F32)
-        xv = _nhwc(x, torch.float32, 4, 0)
+        # guard band: the input inside a larger allocation with NaN on both sides — a read beyond the image (e.g. the 7 zero-weight
+        # pixels behind a 1 x 1 patch) poisons the output instead of multiplying whatever lies there by 0
+        n_in, gpx = B * H * W * 4, 64
+        gbuf = torch.full((n_in + 2 * gpx * 4,), float("nan"), dtype=torch.float32)
+        gbuf[gpx * 4:gpx * 4 + n_in] = x.permute(0, 2, 3, 1).reshape(-1)
+        gbuf = gbuf.to(DEV)
+        xv = View(gbuf[gpx * 4:gpx * 4 + n_in].view(B, H, W, 4), 0, 4)
         ov = View(torch.full((B, Ho, Wo, cout + 4), 7.0, dtype=torch.float32, device=DEV), 4, cout)
         pb.conv_patch(xv, pb.pack_weight_patch(w, 4), pb.upload(b), ov, k, s, p)
         L.launch(pb.ops[0]); _sync()
         got = ov.torch().cpu().double()
         assert (ov.t.float().cpu()[..., :4] == 7.0).all(), "conv_patch wrote outside its channel slice"
+        assert not torch.isnan(got).any(), f"conv_patch read outside its input (k={k}): NaN from the guard band in the output"
         e = rel_err(got, ref)
         pb2 = PlanBuilder(DEV, L.F32)
         o2 = View(torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=DEV), 0, cout)

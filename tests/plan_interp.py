@@ -74,6 +74,142 @@ def _tdt(op):
     return torch.float32 if op.dtype == L.F32 else torch.float16
 
 
+# ---- caption-op semantics: one statement per op family, on LOGICAL tensors (strides / offsets / storage formats resolved by the caller)
+# and in a caller-chosen compute dtype.  run_op calls them with float32 (the interpreter's results); the per-op kernel checks
+# (tests/caption_f64.py::check_caption_f64) call the same functions with float64.  Every function returns its result in `cd`.
+def _nchw(x, cd):
+    return x.permute(0, 3, 1, 2).to(cd)
+
+
+def dwconv3_ref(x, w, b, cd):
+    """x + depthwise_conv3x3(x, zero padding) + b.  x [B,H,W,C], w [3,3,C], b [C] -> [B,H,W,C]."""
+    C = x.shape[-1]
+    xc = _nchw(x, cd)
+    wk = w.permute(2, 0, 1).unsqueeze(1).to(cd)
+    return (F.conv2d(xc, wk, b.to(cd), padding=1, groups=C) + xc).permute(0, 2, 3, 1)
+
+
+def dwconv3_ln_ref(x, w, b, g, be, eps, cd):
+    """(y1, LayerNorm(y1)) with y1 = dwconv3_ref(...) rounded to x's storage dtype (the kernel stores it, the norm reads what is stored)."""
+    y1 = dwconv3_ref(x, w, b, cd).to(x.dtype)
+    return y1, F.layer_norm(y1.to(cd), (x.shape[-1],), g.to(cd), be.to(cd), eps)
+
+
+def layernorm_ref(x, add, g, b, eps, cd):
+    """LayerNorm over the last dim of x [rows, C]; add [period, C] (or None) is added to row r as add[r % period] first."""
+    rows, C = x.shape
+    x = x.to(cd)
+    if add is not None:
+        x = x + add.to(cd).repeat(rows // add.shape[0], 1)
+    return F.layer_norm(x, (C,), g.to(cd), b.to(cd), eps)
+
+
+def _sdpa(q, k, v, scale):
+    return torch.softmax(q @ k.transpose(-2, -1) * scale, -1) @ v
+
+
+def attn_plain_ref(q, k, v, heads, scale, cd):
+    """ATTN_ROWS mode 0: q [G,nq,heads*D], k / v [G,nk,heads*D] -> [G,nq,heads*D] (softmax over all nk keys per head)."""
+    G, nq, C = q.shape
+    nk, D = k.shape[1], C // heads
+    qh, kh, vh = (t.to(cd).reshape(G, -1, heads, D).transpose(1, 2) for t in (q, k, v))
+    return _sdpa(qh, kh, vh, scale).transpose(1, 2).reshape(G, nq, C)
+
+
+def window_partition(t, heads, pad_value=None):
+    """[B,H,W,C] -> [B*wy*wx, heads, 144, D]: 12x12 windows, the image padded to whole windows with pad_value (a [C] row) or zeros."""
+    B, H, W, C = t.shape
+    wy, wx = (H + 11) // 12, (W + 11) // 12
+    pad = torch.zeros(B, wy * 12, wx * 12, C, dtype=t.dtype)
+    if pad_value is not None:
+        pad[:] = pad_value
+    pad[:, :H, :W] = t
+    return pad.view(B, wy, 12, wx, 12, C).permute(0, 1, 3, 2, 4, 5).reshape(B * wy * wx, 144, heads, C // heads).transpose(1, 2)
+
+
+def window_merge(o, B, H, W):
+    """inverse of window_partition (the padding cropped): [B*wy*wx, heads, 144, D] -> [B,H,W,heads*D]."""
+    wy, wx = (H + 11) // 12, (W + 11) // 12
+    C = o.shape[1] * o.shape[3]
+    o = o.transpose(1, 2).reshape(B, wy, wx, 12, 12, C).permute(0, 1, 3, 2, 4, 5).reshape(B, wy * 12, wx * 12, C)
+    return o[:, :H, :W]
+
+
+def attn_window_ref(q, k, v, kbias, vbias, heads, scale, cd):
+    """ATTN_ROWS mode 1 (DaViT window attention): q / k / v [B,H,W,C] (biases already in), attention inside each 12x12 window of the
+    image padded to whole windows; a padded key / value position holds kbias / vbias (what the qkv linear makes of a zero token)."""
+    B, H, W, C = q.shape
+    qw = window_partition(q.to(cd), heads)
+    kw = window_partition(k.to(cd), heads, None if kbias is None else kbias.to(cd))
+    vw = window_partition(v.to(cd), heads, None if vbias is None else vbias.to(cd))
+    return window_merge(_sdpa(qw, kw, vw, scale), B, H, W)
+
+
+def chan_attn_ref(qkv, G, scale, cd):
+    """DaViT channel attention: qkv [B,N,3C] -> [B,N,C]; per group of C/G channels a (C/G)x(C/G) softmax over the N-token products;
+    scale 0 means N^-0.5."""
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    q, k, v = qkv.to(cd).view(B, N, 3, G, C // G).permute(2, 0, 3, 4, 1).unbind(0)          # [B,G,C/G,N]
+    s = scale if scale != 0.0 else N ** -0.5
+    return _sdpa(q, k, v, s).permute(0, 3, 1, 2).reshape(B, N, C)
+
+
+def proj_prep_ref(x, pos, tmp, cd):
+    """projector input: v = (x + pos) + tmp for x [B,N,C]; out [B,N+1,C] = [mean over tokens of v, v]."""
+    v = (x.to(cd) + pos.to(cd)) + tmp.to(cd)
+    return torch.cat([v.mean(1, keepdim=True), v], 1)
+
+
+def embed_step_ref(table, pos_row, ids, C, scale, cd):
+    """decoder token embedding: table rows of ids (a flat [V*C] table) * scale (0 means 1) + one position row."""
+    rows = torch.stack([table[t * C:(t + 1) * C] for t in ids.tolist()]).to(cd) * (scale if scale != 0.0 else 1.0)
+    return rows + pos_row.to(cd)
+
+
+def attn_decode_ref(q, K, V, heads, scale, cd):
+    """one query row per batch row against nk cached keys: q [B,C], K / V [B,nk,C] -> [B,C]."""
+    B, nk, C = K.shape
+    qh = q.to(cd).view(B, heads, 1, C // heads)
+    Kh, Vh = (t.to(cd).view(B, nk, heads, C // heads).transpose(1, 2) for t in (K, V))
+    return _sdpa(qh, Kh, Vh, scale).transpose(1, 2).reshape(B, C)
+
+
+def attn_decode_self_ref(q, Kc, Vc, kn, vn, heads, scale, cd):
+    """decoder self-attention at step st: the st cached rows Kc / Vc [B,st,C] plus this step's kn / vn [B,C] (appended to the cache)."""
+    return attn_decode_ref(q, torch.cat([Kc, kn.unsqueeze(1)], 1), torch.cat([Vc, vn.unsqueeze(1)], 1), heads, scale, cd)
+
+
+def greedy_step_ref(logits, bias, ids, fin, st, max_new, ngram, eos, pad, fbos, feos, cd):
+    """transformers' greedy step (no-repeat-ngram ban, forced BOS / EOS, finished rows emit pad) on logits [B,V] (+ bias [V]); writes
+    ids[:, st + 1] and updates fin in place (ids [B,T] / fin [B] int32); returns the chosen tokens."""
+    cur_len = st + 1
+    logits = logits.to(cd).clone()
+    if bias is not None:
+        logits += bias.to(cd)
+    toks = []
+    for b in range(logits.shape[0]):
+        seq = ids[b, :cur_len].tolist()
+        if ngram > 0 and cur_len + 1 >= ngram:
+            prefix = seq[cur_len - (ngram - 1):]
+            for s0 in range(cur_len - ngram + 1):
+                if seq[s0:s0 + ngram - 1] == prefix:
+                    logits[b, seq[s0 + ngram - 1]] = float("-inf")
+        if fbos >= 0 and cur_len == 1:
+            tok = fbos
+        elif feos >= 0 and cur_len == max_new:
+            tok = feos
+        else:
+            tok = int(torch.argmax(logits[b]))
+        if fin[b]:
+            tok = pad
+        ids[b, st + 1] = tok
+        if not fin[b] and tok == eos:
+            fin[b] = 1
+        toks.append(tok)
+    return toks
+
+
 def run_ops(ops, keep):
     m = Mem(keep)
     for op in ops:
@@ -171,26 +307,21 @@ def run_op(op, m):
         out[..., ocoff:ocoff + C] = y.to(dt)
     elif k == L.OP_DWCONV3:
         B, H, W, C = i[0], i[1], i[2], i[3]
-        x = m.at(p[0], dt)[: B * H * W * C].view(B, H, W, C).permute(0, 3, 1, 2).float()
-        w = m.at(p[1], dt)[: 9 * C].view(3, 3, C).permute(2, 0, 1).unsqueeze(1).float()
-        b = m.at(p[2], torch.float32)[:C]
-        y = F.conv2d(x, w, b, padding=1, groups=C) + x
-        m.at(p[4], dt)[: B * H * W * C].view(B, H, W, C).copy_(y.permute(0, 2, 3, 1).to(dt))
+        x = m.at(p[0], dt)[: B * H * W * C].view(B, H, W, C)
+        y = dwconv3_ref(x, m.at(p[1], dt)[: 9 * C].view(3, 3, C), m.at(p[2], torch.float32)[:C], torch.float32)
+        m.at(p[4], dt)[: B * H * W * C].view(B, H, W, C).copy_(y.to(dt))
     elif k == L.OP_DWCONV3_LN:
         B, H, W, C = i[0], i[1], i[2], i[3]
-        x = m.at(p[0], dt)[: B * H * W * C].view(B, H, W, C).permute(0, 3, 1, 2).float()
-        w = m.at(p[1], dt)[: 9 * C].view(3, 3, C).permute(2, 0, 1).unsqueeze(1).float()
-        y1 = (F.conv2d(x, w, m.at(p[2], torch.float32)[:C], padding=1, groups=C) + x).permute(0, 2, 3, 1).to(dt)
+        x = m.at(p[0], dt)[: B * H * W * C].view(B, H, W, C)
+        y1, hn = dwconv3_ln_ref(x, m.at(p[1], dt)[: 9 * C].view(3, 3, C), m.at(p[2], torch.float32)[:C], m.at(p[5], torch.float32)[:C],
+                                m.at(p[6], torch.float32)[:C], f[0], torch.float32)
         m.at(p[4], dt)[: B * H * W * C].view(B, H, W, C).copy_(y1)
-        hn = F.layer_norm(y1.float(), (C,), m.at(p[5], torch.float32)[:C], m.at(p[6], torch.float32)[:C], f[0])
         m.at(p[3], dt)[: B * H * W * C].view(B, H, W, C).copy_(split_encode(hn.reshape(-1, C)).view(B, H, W, C) if i[6] else hn.to(dt))
     elif k == L.OP_LAYERNORM:
         rows, C, period = i[0] * max(i[1], 1), i[3], i[5]
-        x = m.at(p[0], dt)[: rows * C].view(rows, C).float()
-        if p[1]:
-            add = m.at(p[1], dt)[: period * C].view(period, C).float()
-            x = x + add.repeat(rows // period, 1)
-        y = F.layer_norm(x, (C,), m.at(p[2], torch.float32)[:C], m.at(p[3], torch.float32)[:C], f[0])
+        x = m.at(p[0], dt)[: rows * C].view(rows, C)
+        add = m.at(p[1], dt)[: period * C].view(period, C) if p[1] else None
+        y = layernorm_ref(x, add, m.at(p[2], torch.float32)[:C], m.at(p[3], torch.float32)[:C], f[0], torch.float32)
         if i[6] == 1:
             m.at(p[4], dt)[: rows * C].view(rows, C).copy_(split_encode(y))
         else:
@@ -199,53 +330,33 @@ def run_op(op, m):
                 m.at(p[5], dt)[: rows * C].view(rows, C).copy_(split_encode(y))
     elif k == L.OP_ATTN_ROWS:
         ldq, ldk, ldv, ldo, qoff, koff, voff, ooff, heads, nq, nk, groups, mode, H, W, D = [i[j] for j in range(16)]
-        scale = f[0]
+        C = heads * D
         if mode == 0:
             rows = groups * nq
-            q = m.at(p[0], dt)[: rows * ldq].view(groups, nq, ldq)[..., qoff:qoff + heads * D].float()
-            kx = m.at(p[1], dt)[: groups * nk * ldk].view(groups, nk, ldk)[..., koff:koff + heads * D].float()
-            v = m.at(p[2], dt)[: groups * nk * ldv].view(groups, nk, ldv)[..., voff:voff + heads * D].float()
-            q = q.view(groups, nq, heads, D).transpose(1, 2); kx = kx.view(groups, nk, heads, D).transpose(1, 2)
-            v = v.view(groups, nk, heads, D).transpose(1, 2)
-            o = torch.softmax(q @ kx.transpose(2, 3) * scale, -1) @ v
+            q = m.at(p[0], dt)[: rows * ldq].view(groups, nq, ldq)[..., qoff:qoff + C]
+            kx = m.at(p[1], dt)[: groups * nk * ldk].view(groups, nk, ldk)[..., koff:koff + C]
+            v = m.at(p[2], dt)[: groups * nk * ldv].view(groups, nk, ldv)[..., voff:voff + C]
+            oo = attn_plain_ref(q, kx, v, heads, f[0], torch.float32)
             out = m.at(p[4], dt)[: rows * ldo].view(groups, nq, ldo)
-            oo = o.transpose(1, 2).reshape(groups, nq, heads * D)
-            out[..., ooff:ooff + heads * D] = split_encode(oo.reshape(rows, heads * D)).view(groups, nq, heads * D) if i[16] else oo.to(dt)
+            out[..., ooff:ooff + C] = split_encode(oo.reshape(rows, C)).view(groups, nq, C) if i[16] else oo.to(dt)
         else:
-            wy, wx = (H + 11) // 12, (W + 11) // 12
-            B = groups // (wy * wx)
-            C = heads * D
-            def win(ptr, ld, off, bias):
-                t = m.at(ptr, dt)[: B * H * W * ld].view(B, H, W, ld)[..., off:off + C].float()
-                pad = torch.zeros(B, wy * 12, wx * 12, C)
-                if bias is not None:
-                    pad[:] = bias
-                pad[:, :H, :W] = t
-                pad = pad.view(B, wy, 12, wx, 12, C).permute(0, 1, 3, 2, 4, 5).reshape(B * wy * wx, 144, heads, D)
-                return pad.transpose(1, 2)
+            B = groups // (((H + 11) // 12) * ((W + 11) // 12))
+            q, kx, v = (m.at(ptr, dt)[: B * H * W * ld].view(B, H, W, ld)[..., off:off + C]
+                        for ptr, ld, off in ((p[0], ldq, qoff), (p[1], ldk, koff), (p[2], ldv, voff)))
             kb = m.at(p[5], torch.float32)[:C] if p[5] else None
             vb = m.at(p[6], torch.float32)[:C] if p[6] else None
-            q, kx, v = win(p[0], ldq, qoff, None), win(p[1], ldk, koff, kb), win(p[2], ldv, voff, vb)
-            o = torch.softmax(q @ kx.transpose(2, 3) * scale, -1) @ v
-            o = o.transpose(1, 2).reshape(B, wy, wx, 12, 12, C).permute(0, 1, 3, 2, 4, 5).reshape(B, wy * 12, wx * 12, C)
+            oo = attn_window_ref(q, kx, v, kb, vb, heads, f[0], torch.float32)
             out = m.at(p[4], dt)[: B * H * W * ldo].view(B, H, W, ldo)
-            oo = o[:, :H, :W]
             out[..., ooff:ooff + C] = split_encode(oo.reshape(B * H * W, C)).view(B, H, W, C) if i[16] else oo.to(dt)
     elif k == L.OP_CHAN_ATTN:
         B, N, C, G = i[0], i[1], i[3], i[4]
-        qkv = m.at(p[0], dt)[: B * N * 3 * C].view(B, N, 3, G, C // G).float().permute(2, 0, 3, 4, 1)
-        q, kx, v = qkv.unbind(0)
-        scale = f[0] if f[0] != 0.0 else N ** -0.5
-        o = torch.softmax(q @ kx.transpose(2, 3) * scale, -1) @ v          # [B,G,32,N]
-        oo = o.permute(0, 3, 1, 2).reshape(B, N, C)
+        oo = chan_attn_ref(m.at(p[0], dt)[: B * N * 3 * C].view(B, N, 3 * C), G, f[0], torch.float32)
         m.at(p[4], dt)[: B * N * C].view(B, N, C).copy_(split_encode(oo.reshape(B * N, C)).view(B, N, C) if i[6] else oo.to(dt))
     elif k == L.OP_PROJ_PREP:
         B, N, C = i[0], i[1], i[3]
-        x = m.at(p[0], dt)[: B * N * C].view(B, N, C).float()
-        v = (x + m.at(p[1], torch.float32)[: N * C].view(N, C)) + m.at(p[2], torch.float32)[:C]
-        out = m.at(p[4], dt)[: B * (N + 1) * C].view(B, N + 1, C)
-        out[:, 0] = v.mean(1).to(dt)
-        out[:, 1:] = v.to(dt)
+        y = proj_prep_ref(m.at(p[0], dt)[: B * N * C].view(B, N, C), m.at(p[1], torch.float32)[: N * C].view(N, C),
+                          m.at(p[2], torch.float32)[:C], torch.float32)
+        m.at(p[4], dt)[: B * (N + 1) * C].view(B, N + 1, C).copy_(y.to(dt))
     elif k == L.OP_ASSEMBLE:
         B, n_img, n_txt, C = i[0], i[1], i[2], i[3]
         out = m.at(p[4], dt)[: B * (n_img + n_txt) * C].view(B, n_img + n_txt, C)
@@ -255,15 +366,12 @@ def run_op(op, m):
         B, C, T, off = i[0], i[3], i[4], i[5]
         st = int(m.at(p[6], torch.int32)[0])
         ids = m.at(p[2], torch.int32)[: B * T].view(B, T)[:, st].long()
-        scale = f[0] if f[0] != 0.0 else 1.0
-        table = m.at(p[0], dt)
-        rows = torch.stack([table[t * C:(t + 1) * C] for t in ids.tolist()]).float() * scale
-        pos = m.at(p[1], dt)[(st + off) * C:(st + off + 1) * C].float()
-        m.at(p[4], dt)[: B * C].view(B, C).copy_((rows + pos).to(dt))
+        y = embed_step_ref(m.at(p[0], dt), m.at(p[1], dt)[(st + off) * C:(st + off + 1) * C], ids, C, f[0], torch.float32)
+        m.at(p[4], dt)[: B * C].view(B, C).copy_(y.to(dt))
     elif k == L.OP_ATTN_DECODE:
         ldq, qoff, ldn, koff, voff, ldo, heads, nk_fixed, cap, C, B, ldc = [i[j] for j in range(12)]
         ldc = ldc or C
-        q = m.at(p[0], dt)[: B * ldq].view(B, ldq)[:, qoff:qoff + C].float().view(B, heads, 1, 64)
+        q = m.at(p[0], dt)[: B * ldq].view(B, ldq)[:, qoff:qoff + C]
         kc = m.at(p[3], dt)[: B * cap * ldc - 0].view(-1)
         vc = m.at(p[5], dt).view(-1)
         # cache row r of batch b starts at (b*cap + r)*ldc
@@ -271,47 +379,29 @@ def run_op(op, m):
             n_el = (B * cap - 1) * ldc + C
             t = buf[:n_el]
             idx = (torch.arange(B).view(B, 1) * cap + torch.arange(nk).view(1, nk)) * ldc
+            if nk == 0:
+                return t.new_zeros(B, 0, C)
             return torch.stack([torch.stack([t[o:o + C] for o in row.tolist()]) for row in idx])   # [B,nk,C]
         if nk_fixed > 0:
-            nk = nk_fixed
+            o = attn_decode_ref(q, rows(kc, nk_fixed), rows(vc, nk_fixed), heads, f[0], torch.float32)
         else:
-            st = int(m.at(p[6], torch.int32)[0]); nk = st + 1
+            st = int(m.at(p[6], torch.int32)[0])
             kn = m.at(p[1], dt)[: B * ldn].view(B, ldn)[:, koff:koff + C]
             vn = m.at(p[2], dt)[: B * ldn].view(B, ldn)[:, voff:voff + C]
+            o = attn_decode_self_ref(q, rows(kc, st), rows(vc, st), kn, vn, heads, f[0], torch.float32)
             for b in range(B):
-                o = (b * cap + st) * ldc
-                kc[o:o + C] = kn[b]; vc[o:o + C] = vn[b]
-        K = rows(kc, nk).float().view(B, nk, heads, 64).transpose(1, 2)
-        Vv = rows(vc, nk).float().view(B, nk, heads, 64).transpose(1, 2)
-        o = torch.softmax(q @ K.transpose(2, 3) * f[0], -1) @ Vv
-        m.at(p[4], dt)[: B * ldo].view(B, ldo)[:, :C] = o.transpose(1, 2).reshape(B, C).to(dt)
+                r = (b * cap + st) * ldc
+                kc[r:r + C] = kn[b]; vc[r:r + C] = vn[b]
+        m.at(p[4], dt)[: B * ldo].view(B, ldo)[:, :C] = o.to(dt)
     elif k == L.OP_GREEDY_STEP:
         B, V, ldl, T, max_new, ngram, bos, eos, pad, fbos, feos, inc = [i[j] for j in range(12)]
         step = m.at(p[6], torch.int32)
-        st = int(step[0]); cur_len = st + 1
-        logits = m.at(p[0], dt)[: B * ldl].view(B, ldl)[:, :V].float().clone()
-        if p[1]:
-            logits += m.at(p[1], torch.float32)[:V]
+        st = int(step[0])
+        logits = m.at(p[0], dt)[: B * ldl].view(B, ldl)[:, :V]
+        bias = m.at(p[1], torch.float32)[:V] if p[1] else None
         ids = m.at(p[2], torch.int32)[: B * T].view(B, T)
         fin = m.at(p[3], torch.int32)[:B]
-        for b in range(B):
-            seq = ids[b, :cur_len].tolist()
-            if ngram > 0 and cur_len + 1 >= ngram:
-                prefix = seq[cur_len - (ngram - 1):]
-                for s0 in range(cur_len - ngram + 1):
-                    if seq[s0:s0 + ngram - 1] == prefix:
-                        logits[b, seq[s0 + ngram - 1]] = float("-inf")
-            if fbos >= 0 and cur_len == 1:
-                tok = fbos
-            elif feos >= 0 and cur_len == max_new:
-                tok = feos
-            else:
-                tok = int(torch.argmax(logits[b]))
-            if fin[b]:
-                tok = pad
-            ids[b, st + 1] = tok
-            if not fin[b] and tok == eos:
-                fin[b] = 1
+        greedy_step_ref(logits, bias, ids, fin, st, max_new, ngram, eos, pad, fbos, feos, torch.float32)
         if inc:
             step[0] = st + 1
     elif k == L.OP_CROP_RESIZE:

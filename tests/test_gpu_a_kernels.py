@@ -59,7 +59,7 @@ def test_conv_patch_rows():
     import gpu_checks as G
     r = G.check_conv_patch()
     print(r)
-    assert r["cases"] == 6, r
+    assert r["cases"] == 9, r
 
 
 def test_conv_igemm_exact_f32_path(monkeypatch):

@@ -12,6 +12,23 @@ def test_caption_kernels_vs_interpreter(dtype):
     G.check_caption_ops(dtype)
 
 
+def test_caption_kernels_vs_f64_benched_shapes():
+    """Every caption-op signature of the captioner's plans at the benched 768x768 crops (2 crops; tests/caption_f64.py::GPU_TIER, kept
+    in step with the plans by test_caption_bounds_cpu.py), O(1) and adversarial inputs (sharp softmax, LayerNorm rows at mean 1e3),
+    against float64 references per token / head segment, inside NaN guard bands."""
+    import caption_f64 as CF
+    worst = CF.check_caption_f64(L.F32, tier="gpu")
+    print({k: (f"{v[0]:.2e}", v[2], v[3]) for k, v in worst.items()})
+
+
+@pytest.mark.parametrize("dtype", [L.F32, L.F16])
+def test_caption_kernels_vs_f64_every_branch(dtype):
+    """the emulated tier's cases (every launcher branch, window heads 1-32, channel groups 4-32) on the MI355X itself."""
+    import caption_f64 as CF
+    worst = CF.check_caption_f64(dtype, tier="emu")
+    print({k: (f"{v[0]:.2e}", v[2], v[3]) for k, v in worst.items()})
+
+
 def test_captioner_token_exact_r64():
     """reference cuda-branch shape (64x64 crops, 5 image tokens): greedy ids == transformers CPU."""
     import gpu_checks as G

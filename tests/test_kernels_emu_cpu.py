@@ -47,7 +47,7 @@ def test_conv_patch_rows(emu):
     """row-patch form of the first patch embedding (OMNI_OP_CONV i25) vs f64 and vs the exact-f32 kernel, borders included"""
     import gpu_checks as G
     r = G.check_conv_patch()
-    assert r["cases"] == 6, r
+    assert r["cases"] == 9, r
 
 
 def test_conv_igemm_exact_f32_path(emu, monkeypatch):
@@ -118,6 +118,18 @@ def test_caption_kernels_vs_interpreter(emu, dtype):
     r = G.check_caption_ops(dtype)
     assert dtype != L.F32 or ("attn_window_13" in r and "chan_attn_300" in r and "attn_plain_200_sharp" in r)
 
+
+
+@pytest.mark.parametrize("dtype", [L.F32, L.F16])
+def test_caption_kernels_vs_f64_in_guard_bands(emu, dtype):
+    """Every launcher branch of csrc/caption_ops.hip (the branch -> case table is tests/caption_f64.py::EMU_TIER) against the float64
+    statement of its op, per token / head segment, inside NaN guard bands with wide pitches and nonzero offsets: no read or write
+    outside an operand, every output element written, worst segment error within the family's bound."""
+    import caption_f64 as CF
+    worst = CF.check_caption_f64(dtype, tier="emu")
+    print({k: (f"{v[0]:.2e}", v[2], v[3]) for k, v in worst.items()})
+    assert set(worst) >= {"dwconv3", "dwconv3_ln", "layernorm", "attn_window", "attn_mha", "attn_rows", "chan_attn", "proj_prep",
+                          "assemble", "attn_decode_self", "attn_decode_cross", "embed_step", "greedy_step"}, sorted(worst)
 
 def test_presplit_gemm_accuracy_versus_activation_scale(emu):
     """Format B stores an activation as hi + lo with BOTH halves f16: once |x| < 2^-4 the lo half is subnormal and the pair resolves
