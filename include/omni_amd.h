@@ -168,7 +168,10 @@ enum {
   OMNI_OP_EMBED_STEP = 14,
   /* single-query attention, head_dim 64: self (append k/v at `step` to the cache, attend 0..step) or cross
    * (nk_fixed keys).  p0 q p1 knew p2 vnew p3 kcache [B,cap,C] p5 vcache p4 o [B,ldo] p6 step
-   *  i0 ldq i1 qoff i2 ldn i3 koff i4 voff i5 ldo i6 heads i7 nk_fixed i8 cap i9 C i10 B i11 cache row stride (0 => C); f0 scale */
+   *  i0 ldq i1 qoff i2 ldn i3 koff i4 voff i5 ldo i6 heads i7 nk_fixed i8 cap i9 C i10 B i11 cache row stride (0 => C); f0 scale
+   *  Beam plans (additive; NULL / 0 = the behaviour above): p7 self-attention position table i32 [B, cap], entry [b][t] = the
+   *  cache row that holds position t of row b (row b still appends its own k / v at (b, step)); i12 cross-attention rows per
+   *  cache row: row b reads kcache / vcache row b / i12 (the k beams of a crop share its one cross-K / V row) */
   OMNI_OP_ATTN_DECODE = 15,
   /* greedy decoding step (hf:generation/utils.py:2783-2937 + logits_process NoRepeatNGram/ForcedBOS/ForcedEOS):
    *  p0 logits [B,ldl] p1 final_logits_bias f32 or NULL p2 ids i32[B,T] p3 finished i32[B] p6 step i32*
@@ -238,6 +241,20 @@ enum {
    *     {0,1,2,3, 8,9,10,11, 4,5,6,7, 12,13,14,15} (the order in which the first product's accumulators hold it)
    *  i0*i1 rows i3 C i4 ldi i5 in_coff i12 hidden i13 ldo i14 out_coff i16 ldr i17 res_coff; f1 2^-k1 f2 2^-k2 */
   OMNI_OP_MLP_FUSED = 24,
+  /* beam-search decoding step, transformers' _beam_search (hf:generation/utils.py:3008-3523): per crop (one workgroup), k beams
+   * = decoder rows [b k, b k + k): log_softmax(logits + final_logits_bias) in f32, NoRepeatNGram / ForcedBOS / ForcedEOS on the
+   * log-probs, + running score, top-2k over k x V, next running beams, finished-beam merge with the length penalty, early-stop
+   * heuristic; the crop's rows of p2 / p4 / p5 are reordered in place.  A frozen crop (heuristic satisfied, early_stopping True
+   * with k finished entries, or all 2k candidates stopped) is left as it is.  Ties: lower flat index first.
+   *  p0 logits [B k, ldl] p1 final_logits_bias f32 or NULL p2 running ids i32[B k, T] p3 running scores f32[B k]
+   *  p4 self-attention position table i32[B k, T] (OMNI_OP_ATTN_DECODE p7) p5 finished ids i32[B, k, T] p6 step i32*
+   *  p7 state, 4-byte words: finished scores f32[B, k] | finished flags i32[B, k] | finished lengths i32[B, k] (generated tokens)
+   *     | heuristic unsatisfied i32[B] | frozen i32[B]
+   *  i0 B (crops) i1 vocab i2 ldl i3 T i4 max_new_tokens i5 no_repeat_ngram i6 k (2..8) i7 eos i8 pad i9 forced_bos(-1)
+   *  i10 forced_eos(-1) i11 increment step afterwards i12 early_stopping (0 False, 1 True, 2 "never"); f0 length_penalty.
+   *  3 k T * 4 bytes of LDS <= 48 KB.  The model-level entry points (omni_captioner_*) and plan bundles stay greedy.
+   *  Value 25: the next enumerator after OMNI_OP_MLP_FUSED (implicit, so the explicitly numbered kinds 1..24 stay the list they were). */
+  OMNI_OP_BEAM_STEP,
   OMNI_OP__COUNT
 };
 

@@ -72,7 +72,7 @@ static int dispatch(const omni_op_t* op, hipStream_t s) {
     case OMNI_OP_DWCONV3_LN: return omni_launch_dwconv3_ln(op, s);
     case OMNI_OP_ATTN_ROWS: case OMNI_OP_CHAN_ATTN: case OMNI_OP_ATTN_DECODE: return omni_launch_attention(op, s);
     case OMNI_OP_PROJ_PREP: case OMNI_OP_ASSEMBLE: case OMNI_OP_EMBED_STEP: case OMNI_OP_GREEDY_STEP:
-    case OMNI_OP_CROP_RESIZE: return omni_launch_misc(op, s);
+    case OMNI_OP_BEAM_STEP: case OMNI_OP_CROP_RESIZE: return omni_launch_misc(op, s);
     default:
       omni_set_error("unknown op kind %d", op->kind);
       return OMNI_E_ARG;
@@ -111,6 +111,15 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       ext[4] = span(M, i[13], i[14], Cout);
       ext[5] = i[19] > 0 ? (long long)i[19] * 1024 : 1;
       if (i[24] > 0) ext[6] = (long long)i[24] * 4;          // split-K arrival counters (in-launch combine); p6 is ignored when i24 == 0
+      break;
+    }
+    case OMNI_OP_BEAM_STEP: {
+      const long long rows = (long long)i[0] * i[6], T = i[3];
+      ext[0] = rows > 0 ? ((rows - 1) * i[2] + i[1]) * esz : 1;
+      ext[1] = (long long)i[1] * 4;
+      ext[2] = ext[4] = ext[5] = rows * T * 4;
+      ext[3] = rows * 4;
+      ext[7] = (long long)i[0] * (3LL * i[6] + 2) * 4;
       break;
     }
     case OMNI_OP_MLP_FUSED: {

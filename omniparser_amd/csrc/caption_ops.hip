@@ -12,6 +12,7 @@
 //   embed_step     decoder token embedding + learned position (offset 2)           bart:80-98,594-640
 //   attn_decode    single-query attention with KV-cache append (self) / fixed K,V (cross)
 //   greedy_step    final_logits_bias + NoRepeatNGram + ForcedBOS/EOS + argmax + EOS/pad bookkeeping
+//   beam_step      the same processors on log-probs + top-2k + running / finished beam bookkeeping (hf _beam_search)
 //                  hf:generation/utils.py:2783-2937, hf:generation/logits_process.py:1115-1139,1556,1601
 //   crop_resize    crop -> cv2.resize(64x64, INTER_LINEAR) -> [PIL BICUBIC to RxR] -> /255, normalise
 //                  ref:util/utils.py:97-105,120-123 + hf CLIP image processor
@@ -1707,15 +1708,28 @@ struct DecArgs {
   float scale;
 };
 
-template <typename T>
-__global__ __launch_bounds__(64) void attn_decode_kernel(DecArgs a) {
+// Beam plans (BEAM = true, its own instantiation: the kernels of greedy plans are compiled from BEAM = false and stay as they were):
+// self-attention reads position t of row b from cache row table[b][t] (the rows of a crop's beams share the history they have in
+// common instead of copying it when beams are reordered), cross-attention reads cache row b / kv_div (the k beams of a crop share
+// its single cross-K / V row).
+template <typename T, bool BEAM>
+__device__ __forceinline__ void attn_decode_body(DecArgs a, const int* table, int kv_div) {
   // one wave per (b, head), head_dim 64: lanes split keys for the scores, then split d for P.V
   OMNI_DYN_LDS(float, sp);                    // nk probabilities
   const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   const int C = a.ldc;
   int nk;
-  T* Kc = (T*)a.kc + (long long)b * a.cap * C + h * 64;
-  T* Vc = (T*)a.vc + (long long)b * a.cap * C + h * 64;
+  const int bkv = BEAM && a.nk_fixed > 0 ? b / kv_div : b;
+  T* Kc = (T*)a.kc + (long long)bkv * a.cap * C + h * 64;
+  T* Vc = (T*)a.vc + (long long)bkv * a.cap * C + h * 64;
+  const int* trow = BEAM && a.nk_fixed <= 0 ? table + (long long)b * a.cap : nullptr;
+  // key k of this row: its own cache row, or (self-attention of a beam plan) the row the table names for position k
+  auto krow = [&](int k) -> long long {
+    if constexpr (BEAM) {
+      if (trow) return ((long long)(trow[k] - b) * a.cap + k) * C;
+    }
+    return (long long)k * C;
+  };
   if (a.nk_fixed > 0) {
     nk = a.nk_fixed;
   } else {
@@ -1732,7 +1746,7 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecArgs a) {
   __syncthreads();
   float mx = -INFINITY;
   for (int k = lane; k < nk; k += 64) {
-    const T* kr = Kc + (long long)k * C;
+    const T* kr = Kc + krow(k);
     float s = 0.f;
 #pragma unroll 16
     for (int d = 0; d < 64; ++d) s += sq[d] * ldf(kr + d);
@@ -1746,8 +1760,16 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecArgs a) {
   sum = wave_sum(sum);
   __syncthreads();
   float acc = 0.f;
-  for (int k = 0; k < nk; ++k) acc += sp[k] * ldf(Vc + (long long)k * C + lane);
+  for (int k = 0; k < nk; ++k) acc += sp[k] * ldf(Vc + krow(k) + lane);
   stf((T*)a.o + (long long)b * a.ldo + h * 64 + lane, acc / sum);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void attn_decode_kernel(DecArgs a) { attn_decode_body<T, false>(a, nullptr, 1); }
+
+template <typename T>
+__global__ __launch_bounds__(64) void attn_decode_beam_kernel(DecArgs a, const int* table, int kv_div) {
+  attn_decode_body<T, true>(a, table, kv_div);
 }
 
 // Cross-attention of a decode step (nk_fixed keys, f32 plans), round 3.  The kernel above gives every lane its own K row (64 dword
@@ -1767,6 +1789,79 @@ __global__ __launch_bounds__(256) void attn_decode_cross_kernel(DecArgs a) {
   float* part = red + 8;
   const float* __restrict__ Kc = (const float*)a.kc + (long long)b * a.cap * C + h * 64 + d4;
   const float* __restrict__ Vc = (const float*)a.vc + (long long)b * a.cap * C + h * 64 + d4;
+  const f32x4 q = *reinterpret_cast<const f32x4*>((const float*)a.q + (long long)b * a.ldq + a.qoff + h * 64 + d4);
+  const int per = ((nk + 15) >> 4) << 2;      // keys per wave, a multiple of 4
+  const int k0 = wave * per, k1 = min(k0 + per, nk);
+  float mx = -INFINITY;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  for (int kb = k0; kb < k1; kb += 32) {      // eight 4-key loads in flight; all 64 lanes stay in the loop for the shuffles
+    f32x4 kv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = kb + 4 * u + j;
+      kv[u] = k < k1 ? *reinterpret_cast<const f32x4*>(Kc + (long long)k * C) : z4;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = kb + 4 * u + j;
+      float s = (q[0] * kv[u][0] + q[1] * kv[u][1]) + (q[2] * kv[u][2] + q[3] * kv[u][3]);
+      s += __shfl_xor(s, 8); s += __shfl_xor(s, 4); s += __shfl_xor(s, 2); s += __shfl_xor(s, 1);
+      s *= a.scale;
+      if (k < k1) {
+        if ((lane & 15) == 0) sp[k] = s;
+        mx = fmaxf(mx, s);
+      }
+    }
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int k = tid; k < nk; k += 256) { const float e = expf(sp[k] - mx); sp[k] = e; sum += e; }
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = ((red[4] + red[5]) + red[6]) + red[7];
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int kb = k0; kb < k1; kb += 32) {
+    f32x4 vv[8];
+    float pk[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = kb + 4 * u + j;
+      const bool ok = k < k1;
+      vv[u] = ok ? *reinterpret_cast<const f32x4*>(Vc + (long long)k * C) : z4;
+      pk[u] = ok ? sp[k] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      acc[0] += pk[u] * vv[u][0]; acc[1] += pk[u] * vv[u][1]; acc[2] += pk[u] * vv[u][2]; acc[3] += pk[u] * vv[u][3];
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { acc[e] += __shfl_xor(acc[e], 16); acc[e] += __shfl_xor(acc[e], 32); }
+  if (lane < 16) *reinterpret_cast<f32x4*>(part + wave * 64 + d4) = acc;
+  __syncthreads();
+  if (tid < 64) {
+    const float o = ((part[tid] + part[64 + tid]) + part[128 + tid]) + part[192 + tid];
+    ((float*)a.o)[(long long)b * a.ldo + h * 64 + tid] = o / sum;
+  }
+}
+
+// Beam plans: the kernel above with the cross-K / V row of query row b at b / kv_div (a separate kernel, so that the greedy plans'
+// kernel is compiled exactly as before).
+__global__ __launch_bounds__(256) void attn_decode_cross_beam_kernel(DecArgs a, int kv_div) {
+  OMNI_DYN_LDS(float, sp);                    // [nk] scores -> probabilities, then 8 reduction slots, then [4][64] partial outputs
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int bkv = b / kv_div;                 // the k rows of a crop read its one cross-K / V row
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane >> 4, d4 = (lane & 15) * 4;
+  const int nk = a.nk_fixed, C = a.ldc;
+  float* red = sp + ((nk + 3) & ~3);
+  float* part = red + 8;
+  const float* __restrict__ Kc = (const float*)a.kc + (long long)bkv * a.cap * C + h * 64 + d4;
+  const float* __restrict__ Vc = (const float*)a.vc + (long long)bkv * a.cap * C + h * 64 + d4;
   const f32x4 q = *reinterpret_cast<const f32x4*>((const float*)a.q + (long long)b * a.ldq + a.qoff + h * 64 + d4);
   const int per = ((nk + 15) >> 4) << 2;      // keys per wave, a multiple of 4
   const int k0 = wave * per, k1 = min(k0 + per, nk);
@@ -1897,6 +1992,229 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs a) {
 }
 
 __global__ void step_inc_kernel(int* step) { if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1; }
+
+// ------------------------------------------------------------------------------------ beam_step
+// One step of transformers' _beam_search (hf:generation/utils.py:3008-3523, `_get_top_k_continuations`,
+// `_get_running_beams_for_next_iteration`, `_update_finished_beams`, `_check_early_stop_heuristic`) for one crop per workgroup, k beams
+// = rows [b k, b k + k) of the decoder.  Same f32 arithmetic as hf, including its additive -1e9 sentinels.  Ties between equal scores
+// go to the lower flat index (top-2k over k x V: beam-major; running / finished selections: candidate order, old finished entries
+// before new candidates) — torch.topk promises no order for ties.
+//   state (p7, i32 words): fin_score f32[B][k] | fin_flag[B][k] | fin_len[B][k] (generated tokens, 0 = never written) |
+//                          heuristic_unsatisfied[B] | frozen[B]
+struct BeamArgs {
+  const void* logits; const float* bias; int* ids; float* run_score; int* table; int* fin_ids; const int* step; int* state;
+  int B, V, ldl, T, max_new, ngram, k, eos, pad, forced_bos, forced_eos, early_stopping;   // early_stopping: 0 False, 1 True, 2 "never"
+  float length_penalty;
+};
+
+constexpr int BEAM_MAX = 8, BEAM_LIST = 2 * BEAM_MAX;
+
+__device__ __forceinline__ bool beam_better(float v, int i, float ov, int oi) { return v > ov || (v == ov && i < oi); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
+  OMNI_DYN_LDS(int, stage);                  // [3][k][T]: parents' running ids, parents' table rows, old finished rows
+  __shared__ float red_v[2][4];
+  __shared__ int red_i[2][4];
+  __shared__ float row_red[8];
+  __shared__ int banned[32];
+  __shared__ int nban;
+  __shared__ float cand_v[BEAM_LIST];
+  __shared__ int cand_p[BEAM_LIST], cand_t[BEAM_LIST];
+  __shared__ int run_src[BEAM_MAX], fin_src[BEAM_MAX];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = a.k, K2 = 2 * k, TL = a.T, V = a.V;
+  float* fin_score = reinterpret_cast<float*>(a.state);
+  int* fin_flag = a.state + a.B * k;
+  int* fin_len = a.state + 2 * a.B * k;
+  int* heur = a.state + 3 * a.B * k;
+  int* frozen = heur + a.B;
+  const int st = *a.step;                    // tokens so far = st + 1; this step writes position st + 1
+  if (frozen[b] || st + 1 >= TL) return;      // (uniform over the block)
+  const int cur_len = st + 1;
+  const int row0 = b * k;
+
+  // per-thread top list of (score, flat index) over this thread's strided slice of the crop's k x V candidates, kept sorted
+  float tv[BEAM_LIST];
+  int ti[BEAM_LIST];
+#pragma unroll
+  for (int u = 0; u < BEAM_LIST; ++u) { tv[u] = -INFINITY; ti[u] = 0x7fffffff; }
+  int forced = -1;
+  if (a.forced_bos >= 0 && cur_len == 1) forced = a.forced_bos;
+  if (a.forced_eos >= 0 && cur_len == a.max_new) forced = a.forced_eos;   // cur_len == max_length - 1
+  for (int j = 0; j < k; ++j) {
+    const int r = row0 + j;
+    const T* lg = (const T*)a.logits + (long long)r * a.ldl;
+    const float base = a.run_score[r];
+    if (tid == 0) {
+      int nb = 0;
+      const int* ids = a.ids + (long long)r * TL;
+      if (a.ngram > 0 && cur_len + 1 >= a.ngram) {            // NoRepeatNGram over this beam's own history
+        const int n = a.ngram;
+        for (int i = 0; i + n - 1 < cur_len; ++i) {
+          bool match = true;
+          for (int q = 0; q < n - 1; ++q)
+            if (ids[i + q] != ids[cur_len - (n - 1) + q]) { match = false; break; }
+          if (match && nb < 32) banned[nb++] = ids[i + n - 1];
+        }
+      }
+      nban = nb;
+    }
+    // log_softmax(logits + bias) in f32: max, then sum of exp
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, ldf(lg + v) + (a.bias ? a.bias[v] : 0.0f));
+    mx = wave_max(mx);
+    if (lane == 0) row_red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(row_red[0], row_red[1]), fmaxf(row_red[2], row_red[3]));
+    float sum = 0.f;
+    for (int v = tid; v < V; v += 256) sum += expf(ldf(lg + v) + (a.bias ? a.bias[v] : 0.0f) - mx);
+    sum = wave_sum(sum);
+    if (lane == 0) row_red[4 + wave] = sum;
+    __syncthreads();
+    const float lse = logf(((row_red[4] + row_red[5]) + row_red[6]) + row_red[7]);
+    const int nb = nban;
+    for (int v = tid; v < V; v += 256) {
+      float x;
+      if (forced >= 0) {
+        x = v == forced ? 0.0f : -INFINITY;                   // ForcedBOS / ForcedEOS on the log-probs
+      } else {
+        x = (ldf(lg + v) + (a.bias ? a.bias[v] : 0.0f) - mx) - lse;
+        for (int q = 0; q < nb; ++q) if (banned[q] == v) x = -INFINITY;
+      }
+      x = x + base;
+      const int idx = j * V + v;
+      if (beam_better(x, idx, tv[BEAM_LIST - 1], ti[BEAM_LIST - 1])) {
+        float cv = x; int ci = idx;
+#pragma unroll
+        for (int u = 0; u < BEAM_LIST; ++u) {
+          const bool sw = beam_better(cv, ci, tv[u], ti[u]);
+          const float ov = tv[u]; const int oi = ti[u];
+          tv[u] = sw ? cv : ov; ti[u] = sw ? ci : oi;
+          cv = sw ? ov : cv; ci = sw ? oi : ci;
+        }
+      }
+    }
+    __syncthreads();                                         // row_red / banned are rewritten for the next beam
+  }
+
+  // merge the 256 sorted lists: K2 rounds of a block arg-max over the list heads (each head advances when it wins)
+  int head = 0;
+  for (int c = 0; c < K2; ++c) {
+    float hv = -INFINITY; int hi = 0x7fffffff;
+#pragma unroll
+    for (int u = 0; u < BEAM_LIST; ++u) if (u == head) { hv = tv[u]; hi = ti[u]; }
+    float bv = hv; int bi = hi;
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(bv, off); const int oi = __shfl_xor(bi, off);
+      if (beam_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { red_v[c & 1][wave] = bv; red_i[c & 1][wave] = bi; }
+    __syncthreads();
+    bv = red_v[c & 1][0]; bi = red_i[c & 1][0];
+    for (int w = 1; w < 4; ++w)
+      if (beam_better(red_v[c & 1][w], red_i[c & 1][w], bv, bi)) { bv = red_v[c & 1][w]; bi = red_i[c & 1][w]; }
+    if (hi == bi && head < BEAM_LIST) ++head;
+    if (tid == 0) {
+      cand_v[c] = bv;
+      const bool ok = bi >= 0 && bi < k * V;                  // never: k x V >= 2k entries exist; guards the gathers below
+      cand_p[c] = ok ? bi / V : 0;
+      cand_t[c] = ok ? bi % V : a.pad;
+    }
+  }
+
+  // stage what the reordering reads (parents' rows, old finished rows) before anything is rewritten
+  for (int e = tid; e < k * TL; e += 256) {
+    const int j = e / TL, t = e - j * TL;
+    stage[e] = a.ids[(long long)(row0 + j) * TL + t];
+    stage[k * TL + e] = t <= st ? a.table[(long long)(row0 + j) * TL + t] : 0;
+    stage[2 * k * TL + e] = a.fin_ids[(long long)(row0 + j) * TL + t];
+  }
+  __syncthreads();
+
+  if (tid == 0) {
+    const int gen = cur_len;                                  // generated tokens after this step (decoder prompt = 1 token)
+    bool stopped[BEAM_LIST];
+    bool all_stopped = true;
+    for (int c = 0; c < K2; ++c) {
+      stopped[c] = cand_t[c] == a.eos || cur_len + 1 >= a.max_new + 1;
+      all_stopped = all_stopped && stopped[c];
+    }
+    // next running beams: top k of score - 1e9 * stopped
+    float rk[BEAM_LIST];
+    bool taken[BEAM_LIST + BEAM_MAX];
+    for (int c = 0; c < K2; ++c) { rk[c] = cand_v[c] + (stopped[c] ? -1.0e9f : 0.0f); taken[c] = false; }
+    float new_run[BEAM_MAX];
+    for (int j = 0; j < k; ++j) {
+      int best = -1;
+      for (int c = 0; c < K2; ++c) if (!taken[c] && (best < 0 || rk[c] > rk[best])) best = c;
+      taken[best] = true; run_src[j] = best; new_run[j] = rk[best];
+    }
+    // finished beams: candidates among the first k that stopped, length-penalised, merged with the old k entries
+    bool all_fin = true;
+    for (int j = 0; j < k; ++j) all_fin = all_fin && fin_flag[row0 + j];
+    const bool full = all_fin && a.early_stopping == 1;
+    const bool unsat = heur[b] != 0;
+    const float div = (float)pow((double)gen, (double)a.length_penalty);
+    float ms[BEAM_MAX + BEAM_LIST];
+    bool mf[BEAM_MAX + BEAM_LIST];
+    for (int j = 0; j < k; ++j) { ms[j] = fin_score[row0 + j]; mf[j] = fin_flag[row0 + j] != 0; }
+    for (int c = 0; c < K2; ++c) {
+      const bool did = stopped[c] && c < k;
+      float x = cand_v[c] / div;
+      x = x + (full ? -1.0e9f : 0.0f);
+      x = x + (unsat ? 0.0f : -1.0e9f);
+      x = x + (did ? 0.0f : -1.0e9f);
+      ms[k + c] = x; mf[k + c] = did;
+    }
+    for (int e = 0; e < k + K2; ++e) taken[e] = false;
+    float nfs[BEAM_MAX];
+    bool nff[BEAM_MAX];
+    int nfl[BEAM_MAX];
+    for (int j = 0; j < k; ++j) {
+      int best = -1;
+      for (int e = 0; e < k + K2; ++e) if (!taken[e] && (best < 0 || ms[e] > ms[best])) best = e;
+      taken[best] = true; fin_src[j] = best;
+      nfs[j] = ms[best]; nff[j] = mf[best]; nfl[j] = best < k ? fin_len[row0 + best] : gen;
+    }
+    // early-stop heuristic after cur_len += 1 (sticky), then the crop's frozen flag
+    const int hyp = (a.early_stopping == 2 && a.length_penalty > 0.0f) ? a.max_new : gen;
+    const float best_run = new_run[0] / (float)pow((double)hyp, (double)a.length_penalty);
+    float mn = nfs[0];
+    for (int j = 1; j < k; ++j) mn = fminf(mn, nfs[j]);
+    bool any_better = false, all_new_fin = true;
+    for (int j = 0; j < k; ++j) {
+      any_better = any_better || best_run > (nff[j] ? mn : -1.0e9f);
+      all_new_fin = all_new_fin && nff[j];
+    }
+    const bool unsat_new = unsat && any_better;
+    for (int j = 0; j < k; ++j) {
+      a.run_score[row0 + j] = new_run[j];
+      fin_score[row0 + j] = nfs[j]; fin_flag[row0 + j] = nff[j] ? 1 : 0; fin_len[row0 + j] = nfl[j];
+    }
+    heur[b] = unsat_new ? 1 : 0;
+    frozen[b] = (!unsat_new || (a.early_stopping == 1 && all_new_fin) || all_stopped) ? 1 : 0;
+  }
+  __syncthreads();
+
+  // rewrite the crop's rows from the staged copies: running ids, position table, finished ids
+  for (int e = tid; e < k * TL; e += 256) {
+    const int j = e / TL, t = e - j * TL;
+    const int c = run_src[j], p = cand_p[c];
+    a.ids[(long long)(row0 + j) * TL + t] = t == st + 1 ? cand_t[c] : stage[p * TL + t];
+    if (t <= st) a.table[(long long)(row0 + j) * TL + t] = stage[k * TL + p * TL + t];
+    else if (t == st + 1) a.table[(long long)(row0 + j) * TL + t] = row0 + j;
+    const int f = fin_src[j];
+    int v;
+    if (f < k) {
+      v = stage[2 * k * TL + f * TL + t];
+    } else {
+      const int cf = f - k, pf = cand_p[cf];
+      v = t == st + 1 ? cand_t[cf] : stage[pf * TL + t];
+    }
+    a.fin_ids[(long long)(row0 + j) * TL + t] = v;
+  }
+}
 
 // ------------------------------------------------------------------------------------ crop_resize
 struct CropArgs {
@@ -2162,17 +2480,29 @@ static int launch_attn_decode(const omni_op_t* op, hipStream_t s) {
   a.scale = op->f[0];
   OMNI_REQUIRE(a.q && a.kc && a.vc && a.o && B > 0 && a.heads > 0 && a.C == a.heads * 64, "attn_decode: bad arguments (head_dim 64)");
   OMNI_REQUIRE(a.nk_fixed > 0 || (a.knew && a.vnew && a.step), "attn_decode: self-attention needs new k/v and the step counter");
+  // beam plans: p7 = self-attention position table i32 [B, cap], i12 = rows per cross-K / V row (0 / 1 and NULL = one row each)
+  const int* table = (const int*)op->p[7];
+  const int kv_div = op->i[12] > 1 ? op->i[12] : 1;
+  const bool beam = table != nullptr || kv_div > 1;
+  OMNI_REQUIRE(!table || a.nk_fixed <= 0, "attn_decode: the position table is for self-attention");
+  OMNI_REQUIRE(kv_div == 1 || a.nk_fixed > 0, "attn_decode: rows per K/V row > 1 is for cross-attention");
   int nk_max = a.nk_fixed > 0 ? a.nk_fixed : a.cap;
   if (a.nk_fixed > 0 && op->dtype == OMNI_F32 && a.ldc % 4 == 0 && a.ldq % 4 == 0 && a.qoff % 4 == 0) {
     // cross-attention over the fixed encoder keys: four waves per (row, head), four keys per load instruction
     const size_t lds = (size_t)(((a.nk_fixed + 3) & ~3) + 8 + 256) * 4;
-    hipLaunchKernelGGL(attn_decode_cross_kernel, dim3(a.heads, B), dim3(256), lds, s, a);
+    if (beam)
+      hipLaunchKernelGGL(attn_decode_cross_beam_kernel, dim3(a.heads, B), dim3(256), lds, s, a, kv_div);
+    else
+      hipLaunchKernelGGL(attn_decode_cross_kernel, dim3(a.heads, B), dim3(256), lds, s, a);
     OMNI_HIP_CHECK(hipGetLastError());
     return OMNI_OK;
   }
   dim3 grid(a.heads, B);
   size_t sh = (size_t)nk_max * 4;
-  int rc = by_dtype(op->dtype, "attn_decode",
+  int rc = beam ? by_dtype(op->dtype, "attn_decode",
+      [&] { hipLaunchKernelGGL(attn_decode_beam_kernel<float>, grid, dim3(64), sh, s, a, table, kv_div); },
+      [&] { hipLaunchKernelGGL(attn_decode_beam_kernel<half_t>, grid, dim3(64), sh, s, a, table, kv_div); })
+                : by_dtype(op->dtype, "attn_decode",
       [&] { hipLaunchKernelGGL(attn_decode_kernel<float>, grid, dim3(64), sh, s, a); },
       [&] { hipLaunchKernelGGL(attn_decode_kernel<half_t>, grid, dim3(64), sh, s, a); });
   if (rc) return rc;
@@ -2190,6 +2520,28 @@ static int launch_greedy(const omni_op_t* op, hipStream_t s) {
   int rc = by_dtype(op->dtype, "greedy_step",
       [&] { hipLaunchKernelGGL(greedy_step_kernel<float>, dim3(a.B), dim3(256), 0, s, a); },
       [&] { hipLaunchKernelGGL(greedy_step_kernel<half_t>, dim3(a.B), dim3(256), 0, s, a); });
+  if (rc) return rc;
+  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
+  OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
+static int launch_beam(const omni_op_t* op, hipStream_t s) {
+  BeamArgs a{};
+  a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (int*)op->p[2]; a.run_score = (float*)op->p[3];
+  a.table = (int*)op->p[4]; a.fin_ids = (int*)op->p[5]; a.step = (const int*)op->p[6]; a.state = (int*)op->p[7];
+  a.B = op->i[0]; a.V = op->i[1]; a.ldl = op->i[2]; a.T = op->i[3]; a.max_new = op->i[4]; a.ngram = op->i[5]; a.k = op->i[6];
+  a.eos = op->i[7]; a.pad = op->i[8]; a.forced_bos = op->i[9]; a.forced_eos = op->i[10]; a.early_stopping = op->i[12];
+  a.length_penalty = op->f[0];
+  OMNI_REQUIRE(a.logits && a.ids && a.run_score && a.table && a.fin_ids && a.step && a.state && a.B > 0 && a.V > 0 && a.ldl >= a.V,
+               "beam_step: bad arguments");
+  OMNI_REQUIRE(a.k >= 2 && a.k <= BEAM_MAX, "beam_step: 2 <= beams <= %d (got %d)", BEAM_MAX, a.k);
+  OMNI_REQUIRE(a.T >= a.max_new + 1 && a.max_new >= 1 && a.early_stopping >= 0 && a.early_stopping <= 2, "beam_step: bad arguments");
+  const size_t lds = (size_t)3 * a.k * a.T * 4;
+  OMNI_REQUIRE(lds <= 48 * 1024, "beam_step: %d beams x %d positions exceed the staging LDS", a.k, a.T);
+  int rc = by_dtype(op->dtype, "beam_step",
+      [&] { hipLaunchKernelGGL(beam_step_kernel<float>, dim3(a.B), dim3(256), lds, s, a); },
+      [&] { hipLaunchKernelGGL(beam_step_kernel<half_t>, dim3(a.B), dim3(256), lds, s, a); });
   if (rc) return rc;
   if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
   OMNI_HIP_CHECK(hipGetLastError());
@@ -2259,6 +2611,7 @@ int omni_launch_attention(const omni_op_t* op, hipStream_t s) {
 int omni_launch_misc(const omni_op_t* op, hipStream_t s) {
   switch (op->kind) {
     case OMNI_OP_GREEDY_STEP: return launch_greedy(op, s);
+    case OMNI_OP_BEAM_STEP: return launch_beam(op, s);
     case OMNI_OP_CROP_RESIZE: return launch_crop_resize(op, s);
     case OMNI_OP_PROJ_PREP: case OMNI_OP_ASSEMBLE: case OMNI_OP_EMBED_STEP: return launch_glue(op, s);
     default: omni_set_error("misc: bad kind %d", op->kind); return OMNI_E_ARG;

@@ -210,7 +210,21 @@ class FlorenceWeights:
         fb, fe = g("forced_bos_token_id", None), g("forced_eos_token_id", None)
         self.forced_bos = -1 if fb is None else fb
         self.forced_eos = -1 if fe is None else fe
+        # beam search (Florence2Captioner.generate(num_beams > 1)): transformers' defaults
+        self.length_penalty = float(g("length_penalty", 1.0))
+        self.early_stopping = check_early_stopping(g("early_stopping", False))
         assert self.window == 12 and self.d_model // self.n_heads == 64
+
+
+def check_early_stopping(v):
+    """transformers' `early_stopping`: True, False or "never" (anything else is an error, as there)."""
+    if v is True or v is False or v == "never":
+        return v
+    raise ValueError(f"early_stopping must be True, False or 'never' (got {v!r})")
+
+
+BEAM_MAX = 8                       # include/omni_amd.h OMNI_OP_BEAM_STEP: 2 <= k <= 8
+_EARLY_STOPPING_CODE = {False: 0, True: 1, "never": 2}
 
 
 _DECODE_TUNING = "unset"
@@ -240,13 +254,23 @@ def decode_tuning(device=None):
 # ------------------------------------------------------------------------------------------ plans
 class _StepPlans:
     """The decoder-step plan over B rows (embedding, 6 BART decoder layers with self-KV cache and fixed cross-KV, lm_head, logits
-    processors + arg-max on the device) and its state: shared by _CaptionPlans (encode + decode of one micro-batch) and _DecodePlans."""
+    processors + arg-max on the device) and its state: shared by _CaptionPlans (encode + decode of one micro-batch) and _DecodePlans.
 
-    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None):
+    beam = (k, length_penalty, early_stopping): beam search over B crops = B k decoder rows (crop b owns rows [b k, b k + k)); the
+    cross-attention reads the crop's single cross-K / V row (OMNI_OP_ATTN_DECODE i12 = k), the self-attention reads its history
+    through a position table that OMNI_OP_BEAM_STEP rewrites when beams are reordered (no K / V is copied), and OMNI_OP_BEAM_STEP
+    replaces OMNI_OP_GREEDY_STEP.  `finished` then holds the per-crop frozen flags (nothing can change any more).  beam = None
+    builds the greedy plan, op for op as before."""
+    beam = None
+
+    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None):
         w, dev, dt = cap.w, cap.device, cap.dtype
         sd, wc = w.sd, cap._wcache
         D, nh, lm = w.d_model, w.n_heads, "model.language_model."
         self.T = max_new + 1
+        self.beam = beam
+        kb = beam[0] if beam else 1
+        crops, B = B, B * kb                               # B = decoder rows from here on
         pb = PlanBuilder(dev, dt)                          # weights / tables missing from the model's cache are uploaded through it
 
         def packed(key, make):
@@ -268,9 +292,19 @@ class _StepPlans:
             pd_.conv_tuning = decode_tuning(dev)          # merged decode plans only: the per-micro-batch step plans keep the heuristic
         self.pd = pd_
         T = self.T
-        self.B = B
+        self.B = crops
         self.ids = pd_.raw((B, T), torch.int32)
-        self.finished = pd_.raw((B,), torch.int32)
+        if beam:
+            self.table = pd_.raw((B, T), torch.int32)
+            self.run_score = pd_.raw((B,), torch.float32)
+            self.fin_ids = pd_.raw((crops, kb, T), torch.int32)
+            self.state = pd_.raw((crops * (3 * kb + 2),), torch.int32)     # layout: include/omni_amd.h OMNI_OP_BEAM_STEP p7
+            self.fin_score = self.state[:crops * kb].view(torch.float32).view(crops, kb)
+            self.fin_len = self.state[2 * crops * kb:3 * crops * kb].view(crops, kb)
+            self.heuristic = self.state[3 * crops * kb:3 * crops * kb + crops]
+            self.finished = self.state[3 * crops * kb + crops:]
+        else:
+            self.finished = pd_.raw((B,), torch.int32)
         self.step = pd_.raw((1,), torch.int32)
         esz = 4 if dt == L.F32 else 2
 
@@ -312,7 +346,8 @@ class _StepPlans:
             pre = f"{lm}decoder.layers.{l}."
             dlinear(None, xd, dqkv, keys=[pre + "self_attn.q_proj", pre + "self_attn.k_proj", pre + "self_attn.v_proj"])
             pd_.add_op(L.make_op(L.OP_ATTN_DECODE, dt,
-                                 p=[dqkv.ptr, dqkv.ptr, dqkv.ptr, self.self_k[l].ptr, da.ptr, self.self_v[l].ptr, self.step.data_ptr()],
+                                 p=[dqkv.ptr, dqkv.ptr, dqkv.ptr, self.self_k[l].ptr, da.ptr, self.self_v[l].ptr, self.step.data_ptr()]
+                                 + ([self.table.data_ptr()] if beam else []),
                                  i={0: 3 * D, 1: 0, 2: 3 * D, 3: D, 4: 2 * D, 5: D, 6: nh, 7: 0, 8: T, 9: D, 10: B, 11: D},
                                  f={0: 64 ** -0.5}))
             dlinear(pre + "self_attn.out_proj", da, dt_, res=xd)
@@ -321,7 +356,8 @@ class _StepPlans:
             kv = self.cross_kv[l]
             pd_.add_op(L.make_op(L.OP_ATTN_DECODE, dt,
                                  p=[dq.ptr, None, None, kv.ptr, da.ptr, kv.ptr + D * esz, None],
-                                 i={0: D, 1: 0, 2: 0, 3: 0, 4: 0, 5: D, 6: nh, 7: S, 8: S, 9: D, 10: B, 11: 2 * D},
+                                 i={0: D, 1: 0, 2: 0, 3: 0, 4: 0, 5: D, 6: nh, 7: S, 8: S, 9: D, 10: B, 11: 2 * D,
+                                    **({12: kb} if beam else {})},
                                  f={0: 64 ** -0.5}))
             dlinear(pre + "encoder_attn.out_proj", da, dt_, res=xd)
             dln(pre + "encoder_attn_layer_norm", dt_, xd)
@@ -336,20 +372,52 @@ class _StepPlans:
         if "final_logits_bias" in sd:
             flb = f32("final_logits_bias")
             pd_.keep.append(flb)
-        pd_.add_op(L.make_op(L.OP_GREEDY_STEP, dt,
-                             p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
-                                self.finished.data_ptr(), None, None, self.step.data_ptr()],
-                             i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: w.bos, 7: w.eos, 8: w.pad,
-                                9: w.forced_bos, 10: w.forced_eos, 11: 1}))
+        if beam:
+            pd_.add_op(L.make_op(L.OP_BEAM_STEP, dt,
+                                 p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(), self.run_score.data_ptr(),
+                                    self.table.data_ptr(), self.fin_ids.data_ptr(), self.step.data_ptr(), self.state.data_ptr()],
+                                 i={0: crops, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: kb, 7: w.eos, 8: w.pad,
+                                    9: w.forced_bos, 10: w.forced_eos, 11: 1, 12: _EARLY_STOPPING_CODE[beam[2]]},
+                                 f={0: beam[1]}))
+        else:
+            pd_.add_op(L.make_op(L.OP_GREEDY_STEP, dt,
+                                 p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
+                                    self.finished.data_ptr(), None, None, self.step.data_ptr()],
+                                 i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: w.bos, 7: w.eos, 8: w.pad,
+                                    9: w.forced_bos, 10: w.forced_eos, 11: 1}))
         self.step_flops = pd_.flops
         self.step_plan = pd_.build()
         self.start_token = w.start
+        self.pad_token = w.pad
 
     def reset(self):
+        if self.beam:
+            self._reset_beams()
+            return
         self.ids.zero_()
         self.ids[:, 0] = self.start_token
         self.finished.zero_()
         self.step.zero_()
+
+    def _reset_beams(self):
+        """hf _beam_search's initial state: running scores [0, -1e9, ...], finished scores -1e9, sequences = start token + pad, the
+        early-stop heuristic unsatisfied; every position of a row in its own cache row."""
+        k, B = self.beam[0], self.B
+        self.ids.fill_(self.pad_token)
+        self.ids[:, 0] = self.start_token
+        self.table.copy_(torch.arange(B * k, dtype=torch.int32, device=self.table.device)[:, None].expand(B * k, self.T))
+        self.run_score.view(B, k)[:, 0] = 0.0
+        self.run_score.view(B, k)[:, 1:] = -1.0e9
+        self.fin_ids.fill_(self.pad_token)
+        self.fin_ids[:, :, 0] = self.start_token
+        self.state.zero_()
+        self.fin_score.fill_(-1.0e9)
+        self.heuristic.fill_(1)
+        self.step.zero_()
+
+    def result_ids(self, n: int) -> torch.Tensor:
+        """device ids of the first n crops: the greedy rows, or the best finished hypothesis of each crop"""
+        return self.fin_ids[:n, 0] if self.beam else self.ids[:n]
 
 
 class _DecodePlans(_StepPlans):
@@ -360,7 +428,7 @@ class _DecodePlans(_StepPlans):
     B rows, which then runs its 20 steps once.  Rows are independent: ids per crop are what the per-micro-batch decode produces
     (same kernels; the split-K choice of the step GEMMs, hence the last bits of the logits, depends on the row count)."""
 
-    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int):
+    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, beam=None):
         w, dev, dt = cap.w, cap.device, cap.dtype
         self.B, self.R = B, R
         S = (R // 32) ** 2 + 1 + len(PROMPT_IDS)
@@ -370,7 +438,7 @@ class _DecodePlans(_StepPlans):
         # recycled allocator memory there can hold NaN bit patterns, whose logits are all-NaN rows (found by the one-process GPU suite)
         self.cross_kv = [pk.alloc(B, S, 1, 2 * w.d_model, zero=True) for _ in range(w.dec_layers)]
         self._keep = pk.keep
-        self._build_step(cap, B, max_new, S, self.cross_kv)
+        self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam)
         self.free_evt = None       # recorded behind the decode that last used this plan on another stream (pipelined batches)
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
@@ -390,7 +458,8 @@ class _CaptionPlans(_StepPlans):
     hipGraph — the last micro-batch of a caption batch then computes exactly its own rows instead of a padded bucket (89 rows instead
     of 96 at the benched load), without a second set of activations (~19 GB at 96 rows).  Built on demand by `encode_rows`."""
 
-    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None):
+    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None,
+                 beam=None):
         w, dev, dt = cap.w, cap.device, cap.dtype
         sd = w.sd
         self.B, self.R, self.T = B, R, max_new + 1
@@ -678,7 +747,7 @@ class _CaptionPlans(_StepPlans):
                 self.encode_plan.capture(stream or cap.stream)
             return
         # ---------------- decoder step plan (for a single micro-batch; batches of several micro-batches decode through _DecodePlans)
-        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws)
+        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam)
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)      # allocations / uploads ran on the current stream: order them before cap.stream
         if cap.use_graph:
@@ -758,6 +827,8 @@ class Florence2Captioner:
         self._plans = {}
         self.max_new_tokens = 20
         self.early_exit_every = 5        # poll the all-rows-finished flag every N decode steps (0 = always run max_new_tokens steps)
+        self.num_beams = 1               # caption_crops / ScreenParser: 1 = greedy (the reference's call), k > 1 = beam search
+        self.last_steps = 0              # decode steps the last `_run` / `_decode_merged` issued
         self._lut = None
         self._lock = L.DeviceLock(self.device, reentrant=True)   # one caption batch at a time per model; makes this GPU the thread's current device
 
@@ -858,19 +929,37 @@ class Florence2Captioner:
         sizes[base] = meta[key][0]
         return obj
 
-    @torch.inference_mode()
-    def decode_plans(self, B, R, max_new, slot=0) -> _DecodePlans:
-        """slot: the pipelined stream (pipeline.py::parse_stream) decodes batch i on its own HIP stream while batch i+1 encodes, so it
-        alternates between two decode plans (8 GB of cross-attention K/V each at 384 rows, 768x768 crops)."""
-        key = ("dec", B, R, max_new) if slot == 0 else ("dec", B, R, max_new, slot)
-        return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new))
+    def beam_config(self, num_beams=None, length_penalty=None, early_stopping=None):
+        """(k, length_penalty, early_stopping) of a beam plan, or None for greedy decoding; unset values come from the checkpoint's
+        generation settings (FlorenceWeights)."""
+        k = self.num_beams if num_beams is None else num_beams
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > BEAM_MAX:
+            raise ValueError(f"num_beams must be an integer in 1..{BEAM_MAX} (got {k!r})")
+        if k == 1:
+            return None
+        lp = float(self.w.length_penalty if length_penalty is None else length_penalty)
+        es = check_early_stopping(self.w.early_stopping if early_stopping is None else early_stopping)
+        return (k, lp, es)
 
     @torch.inference_mode()
-    def plans(self, B, R, max_new, slot=0) -> _CaptionPlans:
+    def decode_plans(self, B, R, max_new, slot=0, beam=None) -> _DecodePlans:
+        """slot: the pipelined stream (pipeline.py::parse_stream) decodes batch i on its own HIP stream while batch i+1 encodes, so it
+        alternates between two decode plans (8 GB of cross-attention K/V each at 384 rows, 768x768 crops).  beam: see
+        `beam_config` (B crops = B k decoder rows)."""
+        key = ("dec", B, R, max_new) if slot == 0 else ("dec", B, R, max_new, slot)
+        if beam:
+            key = ("dec", B, R, max_new, slot, beam)
+        return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam))
+
+    @torch.inference_mode()
+    def plans(self, B, R, max_new, slot=0, beam=None) -> _CaptionPlans:
         """slot 1 = a second, independent set of buffers of the same capacity: the pipelined stream (pipeline.py::parse_stream) keeps two
-        128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without)."""
+        128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without).
+        beam: see `beam_config` (the step plan decodes B k rows)."""
         key = (B, R, max_new) if slot == 0 else (B, R, max_new, slot)
-        return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new))
+        if beam:
+            key = (B, R, max_new, slot, beam)
+        return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam))
 
     # ---- merged decode (several micro-batches): encode only, cross-KV into rows [row0, row0 + n) of the decode plan
     def _encode_into(self, cp: _CaptionPlans, n: int, dec: _DecodePlans, row0: int, stream=None):
@@ -889,7 +978,8 @@ class Florence2Captioner:
         run = dec.step_plan.replay if self.use_graph else dec.step_plan.run
         for _ in range(max_new):
             run(stream)
-        return dec.ids[:n].clone()                 # stream-ordered snapshot (read back by the caller)
+        self.last_steps = max_new
+        return dec.result_ids(n).clone()           # stream-ordered snapshot (read back by the caller)
 
     def _lane_stream(self, k):
         # Measured and not kept (round 4, profiles/r4_s2_candidates_ab.txt): CU-masked lane streams (hipExtStreamCreateWithCUMask) and a
@@ -929,14 +1019,20 @@ class Florence2Captioner:
         run = (lambda p: p.replay(self.stream)) if self.use_graph else (lambda p: p.run(self.stream))
         run(cp.encode_plan)
         poll = 0 if defer else self.early_exit_every
+        steps = 0
         for t in range(max_new):
             run(cp.step_plan)
-            # hf stops as soon as every row has emitted EOS (generation/utils.py:2936): poll the device flags every few steps
-            # (a 4-byte read-back) instead of always paying max_new steps; the deferred (batched-stream) path never syncs
+            steps += 1
+            # hf stops as soon as every row has emitted EOS (generation/utils.py:2936) — beam search: as soon as no crop's finished
+            # hypotheses can change (`finished` = frozen flags): poll the device flags every few steps (a 4-byte read-back) instead of
+            # always paying max_new steps; the deferred (batched-stream) path never syncs
             if poll and (t + 1) % poll == 0 and t + 1 < max_new and bool(cp.finished[:n].min().item()):
                 break
+        self.last_steps = steps
         if defer:                          # stream-ordered snapshot; the caller reads it back later (no sync here)
-            return cp.ids[:n].clone()
+            return cp.result_ids(n).clone()
+        if cp.beam:                        # finished hypotheses [n, k, T], their scores and generated lengths (synchronises)
+            return cp.fin_ids[:n].cpu().long(), cp.fin_score[:n].cpu().clone(), cp.fin_len[:n].cpu().long()
         return self._finish_ids(cp.ids[:n].cpu().long())     # synchronises the stream
 
     def _finish_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -953,12 +1049,53 @@ class Florence2Captioner:
         return ids[:, :done_at]
 
     @torch.inference_mode()
-    def generate(self, input_ids=None, pixel_values=None, max_new_tokens=20, num_beams=1, do_sample=False, **kw):
-        """hf-compatible entry point (ref:util/utils.py:125).  pixel_values: [B,3,R,R] float (NCHW)."""
-        if num_beams != 1 or do_sample:
-            raise NotImplementedError("greedy decoding only (the reference calls num_beams=1, do_sample=False)")
+    def generate(self, input_ids=None, pixel_values=None, max_new_tokens=20, num_beams=1, do_sample=False, num_return_sequences=1,
+                 length_penalty=None, early_stopping=None, return_dict_in_generate=False, **kw):
+        """hf-compatible entry point (ref:util/utils.py:125).  pixel_values: [B,3,R,R] float (NCHW).
+
+        num_beams = 1: greedy decoding (the reference's call).  num_beams = 2..8: beam search on the device, transformers'
+        `_beam_search` step for step (OMNI_OP_BEAM_STEP); `num_return_sequences` best hypotheses per image (image-major rows),
+        `length_penalty` / `early_stopping` default to the checkpoint's generation settings.  return_dict_in_generate=True returns
+        an object with `.sequences` and `.sequences_scores` (hf's beam scores; None for greedy decoding).  The default stays
+        num_beams=1 although transformers would take num_beams=3 from Florence-2's generation config: changing it would change what
+        existing callers get.  Sampling is not implemented; the caller's input_ids are not read (fixed <CAPTION> prompt)."""
+        if do_sample:
+            raise NotImplementedError("sampling is not implemented (greedy or beam search decoding)")
+        beam = self.beam_config(num_beams, length_penalty, early_stopping)
+        k = beam[0] if beam else 1
+        if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= k:
+            raise ValueError(f"num_return_sequences must be in 1..num_beams ({k}), got {num_return_sequences!r}")
         with self._lock:
-            return self._generate_locked(pixel_values, max_new_tokens)
+            if beam is None:
+                seq, scores = self._generate_locked(pixel_values, max_new_tokens), None
+            else:
+                seq, scores = self._generate_beams_locked(pixel_values, max_new_tokens, beam, num_return_sequences)
+        return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
+
+    def _beam_outputs(self, parts, nrs):
+        """hf's output of _beam_search (generation/utils.py:3508-3523) from per-chunk (ids [n,k,T], scores [n,k], lengths [n,k]): the
+        best `nrs` hypotheses per image, trimmed to 1 + the longest generated length among the returned ones."""
+        ids = torch.cat([p[0][:, :nrs] for p in parts]).flatten(0, 1)
+        scores = torch.cat([p[1][:, :nrs] for p in parts]).flatten(0, 1)
+        lens = torch.cat([p[2][:, :nrs] for p in parts]).flatten(0, 1)
+        T = 1 + int(lens.max()) if lens.numel() else 1
+        return ids[:, :T].contiguous(), scores
+
+    def _generate_beams_locked(self, pixel_values, max_new_tokens, beam, nrs):
+        Bn, _, R, R2 = pixel_values.shape
+        assert R == R2
+        parts = []
+        for s in range(0, Bn, 128):
+            chunk = pixel_values[s:s + 128]
+            n = chunk.shape[0]
+            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam)
+            if chunk.is_cuda:
+                self.stream.wait_stream(torch.cuda.current_stream(chunk.device))
+            with torch.cuda.stream(self.stream):
+                cp.reset()
+                cp.x_in.t[:n, :, :, :3] = chunk.to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
+                parts.append(self._run(cp, n, max_new_tokens))
+        return self._beam_outputs(parts, nrs)
 
     def _generate_locked(self, pixel_values, max_new_tokens):
         Bn, _, R, R2 = pixel_values.shape
@@ -983,13 +1120,16 @@ class Florence2Captioner:
         return res
 
     @torch.inference_mode()
-    def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128):
+    def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None):
         """Fused fast path: crops are cut, resized (cv2-bilinear 64x64, then Pillow-bicubic to R on the
-        768 path) and normalised on device from the HBM-resident screenshot (ref:util/utils.py:97-123)."""
+        768 path) and normalised on device from the HBM-resident screenshot (ref:util/utils.py:97-123).
+        num_beams: None = `self.num_beams` (default 1, greedy); k > 1 = beam search, the best hypothesis per crop (what
+        generate(num_beams=k) returns for the same pixels)."""
+        beam = self.beam_config(num_beams)
         with self._lock:
-            return self._caption_crops_locked(image_u8, boxes_px, max_new_tokens, batch_size)
+            return self._caption_crops_locked(image_u8, boxes_px, max_new_tokens, batch_size, beam)
 
-    def _caption_crops_locked(self, image_u8, boxes_px, max_new_tokens, batch_size):
+    def _caption_crops_locked(self, image_u8, boxes_px, max_new_tokens, batch_size, beam=None):
         n_all = len(boxes_px)
         R = self.resolution
         outs = []
@@ -1005,7 +1145,7 @@ class Florence2Captioner:
         for s in range(0, n_all, batch_size):
             boxes = boxes_px[s:s + batch_size]
             n = len(boxes)
-            cp = self.plans(self.bucket(n), R, max_new_tokens)
+            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam)
             with torch.cuda.stream(self.stream):
                 cp.reset()
                 bx = torch.tensor(boxes, dtype=torch.int32).to(self.device, non_blocking=True)
@@ -1022,6 +1162,8 @@ class Florence2Captioner:
                 outs.append(self._run(cp, n, max_new_tokens))
         if not outs:
             return torch.zeros((0, 1), dtype=torch.long)
+        if beam:
+            return self._beam_outputs(outs, 1)[0]
         T = max(o.shape[1] for o in outs)
         res = torch.full((n_all, T), self.w.pad, dtype=torch.long)
         o0 = 0

@@ -307,13 +307,15 @@ class ScreenParser:
         # more than one micro-batch: the encode side runs per micro-batch, the 20 decode steps ONCE over all crops
         # (florence.py::_DecodePlans); OMNI_MERGED_DECODE=0 = every micro-batch decodes on its own (A/B knob)
         merged = len(flat) > self.batch_size and os.environ.get("OMNI_MERGED_DECODE", "1") != "0"
+        beam = cap.beam_config()       # cap.num_beams > 1: beam search in the decode plans (the encode-only plans of a merged batch stay greedy)
         # overlap (parse_stream): micro-batches alternate between two encode lanes (HIP streams); 128-row plans exist once per lane, the
         # smaller capacities once — a plan's `free_evt` orders its next use, on whichever lane, behind its last one
         lanes = [cap.encode_lane(k) for k in range(max(1, self.encode_lanes))] if overlap else [cap.stream]
         cap.begin_batch()              # the plan sets this batch takes from the captioner's cache stay resident until the next batch
         if overlap and merged:
             self._dec_slot = 1 - getattr(self, "_dec_slot", 1)
-        dec = cap.decode_plans(cap.decode_bucket(len(flat)), R, max_new_tokens, slot=self._dec_slot if overlap else 0) if merged else None
+        bkw = {"beam": beam} if beam else {}
+        dec = cap.decode_plans(cap.decode_bucket(len(flat)), R, max_new_tokens, slot=self._dec_slot if overlap else 0, **bkw) if merged else None
         if merged and not overlap:
             with torch.cuda.stream(cap.stream):
                 dec.reset()
@@ -333,7 +335,7 @@ class ScreenParser:
             if merged and cap.exact_rows and n < self.batch_size:
                 cp = cap.plans(cap.bucket(self.batch_size), R, max_new_tokens, slot=lane)
             else:
-                cp = cap.plans(cap.bucket(n), R, max_new_tokens, slot=lane if n == self.batch_size else 0)
+                cp = cap.plans(cap.bucket(n), R, max_new_tokens, slot=lane if n == self.batch_size else 0, **({} if merged else bkw))
             with torch.cuda.stream(stream):
                 if cp.free_evt is not None:
                     stream.wait_event(cp.free_evt)

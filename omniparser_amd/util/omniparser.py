@@ -49,6 +49,13 @@ class Omniparser(object):
             if res not in (64, 768):
                 raise ValueError(f"caption_resolution must be 64 or 768, got {res}")
             self.caption_model_processor["model"].resolution = res
+        # beam width of the captioner's decoder: 1 (default) = greedy, the reference's call (ref:util/utils.py:125); 2..8 = beam
+        # search, the best hypothesis per crop.  Like caption_resolution, an explicit choice set on the caption model.
+        if config.get("caption_num_beams") is not None:
+            nb = config["caption_num_beams"]
+            if isinstance(nb, bool) or not isinstance(nb, int) or not 1 <= nb <= 8:
+                raise ValueError(f"caption_num_beams must be an integer in 1..8, got {nb!r}")
+            self.caption_model_processor["model"].num_beams = nb
 
     def _ocr(self, image: Image.Image, ocr=None):
         """`ocr` = (texts, xyxy px boxes) handed over by the caller for THIS image; else the configured provider."""
