@@ -1779,82 +1779,12 @@ __global__ __launch_bounds__(64) void attn_decode_beam_kernel(DecArgs a, const i
 // 16 lanes of a key reduce their partial dot products with four xor-shuffles, eight such loads are in flight per lane.  P.V uses
 // the same mapping (a lane accumulates its slot over its keys, the four key lanes are folded at the end) and the four waves are
 // summed in wave order through LDS.  Same softmax (expf, max-subtracted), different summation order than the kernel above.
-__global__ __launch_bounds__(256) void attn_decode_cross_kernel(DecArgs a) {
+// BEAM = true (beam plans): query row b reads cross-K / V row b / kv_div; greedy plans launch BEAM = false with kv_div = 1.
+template <bool BEAM>
+__global__ __launch_bounds__(256) void attn_decode_cross_kernel(DecArgs a, int kv_div) {
   OMNI_DYN_LDS(float, sp);                    // [nk] scores -> probabilities, then 8 reduction slots, then [4][64] partial outputs
   const int h = blockIdx.x, b = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j = lane >> 4, d4 = (lane & 15) * 4;
-  const int nk = a.nk_fixed, C = a.ldc;
-  float* red = sp + ((nk + 3) & ~3);
-  float* part = red + 8;
-  const float* __restrict__ Kc = (const float*)a.kc + (long long)b * a.cap * C + h * 64 + d4;
-  const float* __restrict__ Vc = (const float*)a.vc + (long long)b * a.cap * C + h * 64 + d4;
-  const f32x4 q = *reinterpret_cast<const f32x4*>((const float*)a.q + (long long)b * a.ldq + a.qoff + h * 64 + d4);
-  const int per = ((nk + 15) >> 4) << 2;      // keys per wave, a multiple of 4
-  const int k0 = wave * per, k1 = min(k0 + per, nk);
-  float mx = -INFINITY;
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  for (int kb = k0; kb < k1; kb += 32) {      // eight 4-key loads in flight; all 64 lanes stay in the loop for the shuffles
-    f32x4 kv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = kb + 4 * u + j;
-      kv[u] = k < k1 ? *reinterpret_cast<const f32x4*>(Kc + (long long)k * C) : z4;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = kb + 4 * u + j;
-      float s = (q[0] * kv[u][0] + q[1] * kv[u][1]) + (q[2] * kv[u][2] + q[3] * kv[u][3]);
-      s += __shfl_xor(s, 8); s += __shfl_xor(s, 4); s += __shfl_xor(s, 2); s += __shfl_xor(s, 1);
-      s *= a.scale;
-      if (k < k1) {
-        if ((lane & 15) == 0) sp[k] = s;
-        mx = fmaxf(mx, s);
-      }
-    }
-  }
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
-  for (int k = tid; k < nk; k += 256) { const float e = expf(sp[k] - mx); sp[k] = e; sum += e; }
-  sum = wave_sum(sum);
-  if (lane == 0) red[4 + wave] = sum;
-  __syncthreads();
-  sum = ((red[4] + red[5]) + red[6]) + red[7];
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int kb = k0; kb < k1; kb += 32) {
-    f32x4 vv[8];
-    float pk[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = kb + 4 * u + j;
-      const bool ok = k < k1;
-      vv[u] = ok ? *reinterpret_cast<const f32x4*>(Vc + (long long)k * C) : z4;
-      pk[u] = ok ? sp[k] : 0.0f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      acc[0] += pk[u] * vv[u][0]; acc[1] += pk[u] * vv[u][1]; acc[2] += pk[u] * vv[u][2]; acc[3] += pk[u] * vv[u][3];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { acc[e] += __shfl_xor(acc[e], 16); acc[e] += __shfl_xor(acc[e], 32); }
-  if (lane < 16) *reinterpret_cast<f32x4*>(part + wave * 64 + d4) = acc;
-  __syncthreads();
-  if (tid < 64) {
-    const float o = ((part[tid] + part[64 + tid]) + part[128 + tid]) + part[192 + tid];
-    ((float*)a.o)[(long long)b * a.ldo + h * 64 + tid] = o / sum;
-  }
-}
-
-// Beam plans: the kernel above with the cross-K / V row of query row b at b / kv_div (a separate kernel, so that the greedy plans'
-// kernel is compiled exactly as before).
-__global__ __launch_bounds__(256) void attn_decode_cross_beam_kernel(DecArgs a, int kv_div) {
-  OMNI_DYN_LDS(float, sp);                    // [nk] scores -> probabilities, then 8 reduction slots, then [4][64] partial outputs
-  const int h = blockIdx.x, b = blockIdx.y;
-  const int bkv = b / kv_div;                 // the k rows of a crop read its one cross-K / V row
+  const int bkv = BEAM ? b / kv_div : b;      // beam plans: the k rows of a crop read its one cross-K / V row
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane >> 4, d4 = (lane & 15) * 4;
   const int nk = a.nk_fixed, C = a.ldc;
@@ -2491,9 +2421,9 @@ static int launch_attn_decode(const omni_op_t* op, hipStream_t s) {
     // cross-attention over the fixed encoder keys: four waves per (row, head), four keys per load instruction
     const size_t lds = (size_t)(((a.nk_fixed + 3) & ~3) + 8 + 256) * 4;
     if (beam)
-      hipLaunchKernelGGL(attn_decode_cross_beam_kernel, dim3(a.heads, B), dim3(256), lds, s, a, kv_div);
+      hipLaunchKernelGGL(attn_decode_cross_kernel<true>, dim3(a.heads, B), dim3(256), lds, s, a, kv_div);
     else
-      hipLaunchKernelGGL(attn_decode_cross_kernel, dim3(a.heads, B), dim3(256), lds, s, a);
+      hipLaunchKernelGGL(attn_decode_cross_kernel<false>, dim3(a.heads, B), dim3(256), lds, s, a, 1);
     OMNI_HIP_CHECK(hipGetLastError());
     return OMNI_OK;
   }

@@ -252,6 +252,47 @@ def decode_tuning(device=None):
 
 
 # ------------------------------------------------------------------------------------------ plans
+class _Weights:
+    """The model's device weights and tables, shared by every plan of a captioner (`cap._wcache`, keyed by (key, dtype[, variant]):
+    the tests hand one cache to several captioners).  An entry missing from the cache is built on first use, uploaded through `pb`."""
+
+    def __init__(self, cap: "Florence2Captioner", pb: PlanBuilder):
+        self.sd, self.wc, self.dt, self.pb = cap.w.sd, cap._wcache, cap.dtype, pb
+
+    def cached(self, ck, build):
+        if ck not in self.wc:
+            self.wc[ck] = build()
+        return self.wc[ck]
+
+    def packed(self, key, make, dma=False):
+        """(packed weight, f32 bias or None) of make() = (weight, bias or None): format B of the LDS-DMA GEMM (dma) or conv layout"""
+        def build():
+            wt, b = make()
+            return (self.pb.pack_weight_dma(wt) if dma else self.pb.pack_weight(wt if wt.dim() == 4 else wt[:, :, None, None]),
+                    self.pb.upload(b.float()) if b is not None else None)
+        return self.cached((key, self.dt, "dma") if dma else (key, self.dt), build)
+
+    def linear(self, keys, bias=True, dma=False):
+        """`packed` of the nn.Linear layers `keys` concatenated along the output axis (q|k|v, k|v: one GEMM)"""
+        sd = self.sd
+        return self.packed("|".join(keys), lambda: (torch.cat([sd[k + ".weight"] for k in keys], 0),
+                                                    torch.cat([sd[k + ".bias"] for k in keys], 0) if bias else None), dma)
+
+    def f32(self, key):
+        return self.cached((key, "f32"), lambda: self.pb.upload(self.sd[key].float()))
+
+    def dwconv(self, key):
+        """depthwise 3x3 convolution: weight [C,1,3,3] -> [3][3][C] in the plan dtype, f32 bias"""
+        wt, b = self.sd[key + ".weight"], self.sd[key + ".bias"]
+        return self.cached((key, self.dt), lambda: (self.pb.upload(wt[:, 0].permute(1, 2, 0).contiguous().to(torch_dtype(self.dt))),
+                                                    self.pb.upload(b.float())))
+
+    def layernorm(self, key, x, out, rows, C, add=None, y2=None, period=0, omode=0, eps=1e-5):
+        """OMNI_OP_LAYERNORM over `rows` rows of C channels (device addresses x, add, out, y2) with the affine parameters of `key`"""
+        return L.make_op(L.OP_LAYERNORM, self.dt, p=[x, add, self.f32(key + ".weight").data_ptr(), self.f32(key + ".bias").data_ptr(), out, y2],
+                         i={0: rows, 1: 1, 3: C, 5: period, 6: omode}, f={0: eps})
+
+
 class _StepPlans:
     """The decoder-step plan over B rows (embedding, 6 BART decoder layers with self-KV cache and fixed cross-KV, lm_head, logits
     processors + arg-max on the device) and its state: shared by _CaptionPlans (encode + decode of one micro-batch) and _DecodePlans.
@@ -265,27 +306,13 @@ class _StepPlans:
 
     def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None):
         w, dev, dt = cap.w, cap.device, cap.dtype
-        sd, wc = w.sd, cap._wcache
+        sd = w.sd
         D, nh, lm = w.d_model, w.n_heads, "model.language_model."
         self.T = max_new + 1
         self.beam = beam
         kb = beam[0] if beam else 1
         crops, B = B, B * kb                               # B = decoder rows from here on
-        pb = PlanBuilder(dev, dt)                          # weights / tables missing from the model's cache are uploaded through it
-
-        def packed(key, make):
-            ck = (key, dt)
-            if ck not in wc:
-                wt, b = make()
-                wc[ck] = (pb.pack_weight(wt if wt.dim() == 4 else wt[:, :, None, None]), pb.upload(b.float()) if b is not None else None)
-            return wc[ck]
-
-        def f32(key):
-            ck = (key, "f32")
-            if ck not in wc:
-                wc[ck] = pb.upload(sd[key].float())
-            return wc[ck]
-
+        W = _Weights(cap, PlanBuilder(dev, dt))            # weights / tables missing from the model's cache are uploaded through its builder
         pd_ = PlanBuilder(dev, dt)
         pd_.ws = ws
         if isinstance(self, _DecodePlans):
@@ -308,26 +335,14 @@ class _StepPlans:
         self.step = pd_.raw((1,), torch.int32)
         esz = 4 if dt == L.F32 else 2
 
-        def dlinear(key, xin: View, out: View, act=L.ACT_NONE, res=None, keys=None, bias=True):
-            keys = keys or [key]
-            def make():
-                wt = torch.cat([sd[k + ".weight"] for k in keys], 0)
-                b = torch.cat([sd[k + ".bias"] for k in keys], 0) if bias else None
-                return wt, b
-            wp, bp = packed("|".join(keys), make)
-            return pd_.conv(xin, wp, bp, out, 1, act=act, res=res)
+        def dlinear(key, xin: View, out: View, act=L.ACT_NONE, res=None, keys=None):
+            return pd_.conv(xin, *W.linear(keys or [key]), out, 1, act=act, res=res)
 
         def dln(key, xin: View, out: View):
-            pd_.add_op(L.make_op(L.OP_LAYERNORM, dt, p=[xin.ptr, None, f32(key + ".weight").data_ptr(),
-                                                       f32(key + ".bias").data_ptr(), out.ptr],
-                                 i={0: B, 1: 1, 3: D, 5: 0}, f={0: 1e-5}))
-            return out
+            pd_.add_op(W.layernorm(key, xin.ptr, out.ptr, B, D))
 
-        ck = ("dectab", dt)
-        if ck not in wc:
-            wc[ck] = (pb.upload(sd[lm + "shared.weight"].to(torch_dtype(dt))),
-                      pb.upload(sd[lm + "decoder.embed_positions.weight"].to(torch_dtype(dt))))
-        table, dpos = wc[ck]
+        table, dpos = W.cached(("dectab", dt), lambda: (W.pb.upload(sd[lm + "shared.weight"].to(torch_dtype(dt))),
+                                                        W.pb.upload(sd[lm + "decoder.embed_positions.weight"].to(torch_dtype(dt)))))
         pd_.keep += [table, dpos]
         e = pd_.alloc(B, 1, 1, D)
         pd_.add_op(L.make_op(L.OP_EMBED_STEP, dt, p=[table.data_ptr(), dpos.data_ptr(), self.ids.data_ptr(), None, e.ptr,
@@ -366,11 +381,11 @@ class _StepPlans:
             dln(pre + "final_layer_norm", dt_, xd)
         logits = pd_.alloc(B, 1, 1, w.vocab)
         self.logits = logits
-        wp, _ = packed("lm_head", lambda: (sd["lm_head.weight"], None))
+        wp, _ = W.packed("lm_head", lambda: (sd["lm_head.weight"], None))
         pd_.conv(xd, wp, None, logits, 1)
         flb = None
         if "final_logits_bias" in sd:
-            flb = f32("final_logits_bias")
+            flb = W.f32("final_logits_bias")
             pd_.keep.append(flb)
         if beam:
             pd_.add_op(L.make_op(L.OP_BEAM_STEP, dt,
@@ -419,6 +434,19 @@ class _StepPlans:
         """device ids of the first n crops: the greedy rows, or the best finished hypothesis of each crop"""
         return self.fin_ids[:n, 0] if self.beam else self.ids[:n]
 
+    def _warm_up_and_capture(self, cap, *plans):
+        """run the plans once on the captioner's stream (first launches outside a capture), then capture each as a hipGraph"""
+        if cap.device.type == "cuda":
+            torch.cuda.synchronize(cap.device)      # allocations / uploads ran on the current stream: order them before cap.stream
+        if cap.use_graph:
+            self.reset()
+            for p in plans:
+                p.run(cap.stream)
+            cap.stream.synchronize()
+            for p in plans:
+                p.capture(cap.stream)
+            cap.stream.synchronize()
+
 
 class _DecodePlans(_StepPlans):
     """Decode for the crops of SEVERAL caption micro-batches at once.  The encode side of a batch of screenshots runs in micro-batches
@@ -440,14 +468,7 @@ class _DecodePlans(_StepPlans):
         self._keep = pk.keep
         self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam)
         self.free_evt = None       # recorded behind the decode that last used this plan on another stream (pipelined batches)
-        if dev.type == "cuda":
-            torch.cuda.synchronize(dev)
-        if cap.use_graph:
-            self.reset()
-            self.step_plan.run(cap.stream)
-            cap.stream.synchronize()
-            self.step_plan.capture(cap.stream)
-            cap.stream.synchronize()
+        self._warm_up_and_capture(cap, self.step_plan)
 
 
 class _CaptionPlans(_StepPlans):
@@ -472,7 +493,7 @@ class _CaptionPlans(_StepPlans):
         self._row_plans = {}      # n -> encode-only plan set of exactly n rows in THIS plan set's buffers (encode_rows), LRU
         self.pb = pb
         V = pb.V
-        wc = cap._wcache
+        W = _Weights(cap, pb)
 
         # f32 plans run the encode-side linear layers on the pre-split LDS-DMA GEMM (csrc/gemm_dma.hip): weights in format B,
         # inputs written pre-split by their producers.  OMNI_GEMM_DMA=0 keeps every layer on the register-staged kernels.
@@ -483,20 +504,6 @@ class _CaptionPlans(_StepPlans):
         # the width is a multiple of 128 — true for all Florence-2 widths (128..1024, 768); narrower stand-ins stay on f32 tensors
         grp = {"dma": use_dma}
 
-        def packed(key, make, dma=False):
-            ck = (key, dt, "dma") if dma else (key, dt)
-            if ck not in wc:
-                wt, b = make()
-                wc[ck] = (pb.pack_weight_dma(wt) if dma else pb.pack_weight(wt if wt.dim() == 4 else wt[:, :, None, None]),
-                          pb.upload(b.float()) if b is not None else None)
-            return wc[ck]
-
-        def f32(key):
-            ck = (key, "f32")
-            if ck not in wc:
-                wc[ck] = pb.upload(sd[key].float())
-            return wc[ck]
-
         def tokens(v: View) -> View:
             return View(v.t.view(v.B, v.H * v.W, 1, v.ld), v.coff, v.C, v.fmt)
 
@@ -504,14 +511,10 @@ class _CaptionPlans(_StepPlans):
             """nn.Linear.  With the LDS-DMA GEMM an f32 input is converted to format B IN PLACE first (callers only pass
             tensors whose f32 content nobody else reads); out_split: the epilogue writes format B for the next GEMM."""
             keys = keys or [key]
-            def make():
-                wt = torch.cat([sd[k + ".weight"] for k in keys], 0)
-                b = torch.cat([sd[k + ".bias"] for k in keys], 0) if bias else None
-                return wt, b
             n_out, k_in = out.C, x.C
             dma = grp["dma"] and n_out % 128 == 0 and k_in % 32 == 0 and x.ld % 16 == 0 and x.coff % 16 == 0
             assert dma or x.fmt != "split", f"{keys}: split input for a layer that cannot take the LDS-DMA GEMM"
-            wp, bp = packed("|".join(keys), make, dma=dma)
+            wp, bp = W.linear(keys, bias, dma)
             if dma and x.fmt != "split":
                 pb.split_convert(x)
             xt, ot = tokens(x), tokens(out)
@@ -526,21 +529,15 @@ class _CaptionPlans(_StepPlans):
             omode, y2 = 0, None
             if grp["dma"] and split is not None and x.C % 16 == 0:
                 omode, y2 = (1, None) if split is out else (2, split)
-            pb.add_op(L.make_op(L.OP_LAYERNORM, dt, p=[x.ptr, add.data_ptr() if add is not None else None,
-                                                      f32(key + ".weight").data_ptr(), f32(key + ".bias").data_ptr(), out.ptr,
-                                                      y2.ptr if y2 is not None else None],
-                                i={0: rows, 1: 1, 3: x.C, 5: period, 6: omode}, f={0: eps}))
+            pb.add_op(W.layernorm(key, x.ptr, out.ptr, rows, x.C, add=add.data_ptr() if add is not None else None,
+                                  y2=y2.ptr if y2 is not None else None, period=period, omode=omode, eps=eps))
             out.fmt = "split" if omode == 1 else "f32"
             if y2 is not None:
                 y2.fmt = "split"
             return out
 
         def dwconv(key, x: View, out: View):
-            ck = (key, dt)
-            if ck not in wc:
-                wt = sd[key + ".weight"]                      # [C,1,3,3] -> [3][3][C]
-                wc[ck] = (pb.upload(wt[:, 0].permute(1, 2, 0).contiguous().to(torch_dtype(dt))), pb.upload(sd[key + ".bias"].float()))
-            wp, bp = wc[ck]
+            wp, bp = W.dwconv(key)
             pb.keep += [wp, bp]
             pb.add_op(L.make_op(L.OP_DWCONV3, dt, p=[x.ptr, wp.data_ptr(), bp.data_ptr(), None, out.ptr],
                                 i={0: x.B, 1: x.H, 2: x.W, 3: x.C}))
@@ -558,15 +555,11 @@ class _CaptionPlans(_StepPlans):
             if not (fuse_env and dt == L.F32 and x.C in (128, 256, 512)):
                 dwconv(conv_key, x, y1)
                 return layernorm(norm_key, y1, hout, split=hout)      # hbuf only feeds qkv / fc1
-            ck = (conv_key, dt)
-            if ck not in wc:
-                wt = sd[conv_key + ".weight"]
-                wc[ck] = (pb.upload(wt[:, 0].permute(1, 2, 0).contiguous().to(torch_dtype(dt))), pb.upload(sd[conv_key + ".bias"].float()))
-            wp, bp = wc[ck]
+            wp, bp = W.dwconv(conv_key)
             pb.keep += [wp, bp]
             pb.add_op(L.make_op(L.OP_DWCONV3_LN, dt,
                                 p=[x.ptr, wp.data_ptr(), bp.data_ptr(), hout.ptr, y1.ptr,
-                                   f32(norm_key + ".weight").data_ptr(), f32(norm_key + ".bias").data_ptr()],
+                                   W.f32(norm_key + ".weight").data_ptr(), W.f32(norm_key + ".bias").data_ptr()],
                                 i={0: x.B, 1: x.H, 2: x.W, 3: x.C, 6: 1 if grp["dma"] else 0}, f={0: 1e-5}))
             hout.fmt = "split" if grp["dma"] else "f32"
             return hout
@@ -587,7 +580,7 @@ class _CaptionPlans(_StepPlans):
                 xn = pb.alloc(B, x.H, x.W, x.C)
                 layernorm(f"{vt}convs.{s}.norm", x, xn)
                 cur = pb.alloc(B, Ho, Ho, C)
-                wp, bp = packed(conv_key, lambda ck=conv_key: (sd[ck + ".weight"], sd[ck + ".bias"]))
+                wp, bp = W.packed(conv_key, lambda: (sd[conv_key + ".weight"], sd[conv_key + ".bias"]))
                 pb.conv(xn, wp, bp, cur, k, st, pd)
                 pb.release(xn, *([] if x is self.x_in else [x]))   # reuse_activations: the previous stage's output has had its last reader
             else:
@@ -595,16 +588,12 @@ class _CaptionPlans(_StepPlans):
                 if cap.patch_rows and dt == L.F32 and pb.split and V == 4 and k <= 8 and x is self.x_in:
                     # the 7 x 7 / stride-4 patch embedding over the 3 (stored: 4) input channels as a 7 x 1 convolution over 8 consecutive
                     # pixels on the split-f16 MFMA kernel (PlanBuilder.conv_patch) instead of K = 196 on the exact-f32 one (81 TF/s)
-                    ck2 = (conv_key, dt, "patch")
-                    if ck2 not in wc:
-                        wc[ck2] = (pb.pack_weight_patch(sd[conv_key + ".weight"], V), pb.upload(sd[conv_key + ".bias"].float()))
-                    wp, bp = wc[ck2]
+                    wp, bp = W.cached((conv_key, dt, "patch"), lambda: (pb.pack_weight_patch(sd[conv_key + ".weight"], V),
+                                                                         pb.upload(sd[conv_key + ".bias"].float())))
                     pb.conv_patch(x, wp, bp, t0, k, st, pd)
                 else:
-                    ck2 = (conv_key, dt, "pad")
-                    if ck2 not in wc:
-                        wc[ck2] = (pb.pack_weight(sd[conv_key + ".weight"], cin_pad=V), pb.upload(sd[conv_key + ".bias"].float()))
-                    wp, bp = wc[ck2]
+                    wp, bp = W.cached((conv_key, dt, "pad"), lambda: (pb.pack_weight(sd[conv_key + ".weight"], cin_pad=V),
+                                                                       pb.upload(sd[conv_key + ".bias"].float())))
                     pb.conv(x, wp, bp, t0, k, st, pd)
                 cur = pb.alloc(B, Ho, Ho, C)
                 layernorm(f"{vt}convs.{s}.norm", t0, cur)
@@ -628,7 +617,7 @@ class _CaptionPlans(_StepPlans):
                     dwconv_ln(pre + "conv1", pre + "norm1", A_, B_, hbuf)
                     if kind == "spatial_block":
                         linear(pre + "window_attn.qkv", hbuf, qkv)
-                        qb = f32(pre + "window_attn.qkv.bias")
+                        qb = W.f32(pre + "window_attn.qkv.bias")
                         nw = ((H + 11) // 12) ** 2
                         pb.add_op(L.make_op(
                             L.OP_ATTN_ROWS, dt,
@@ -647,11 +636,9 @@ class _CaptionPlans(_StepPlans):
                     dwconv_ln(pre + "conv2", pre + "norm2", B_, A_, hbuf)
                     if mlp_one:
                         k1, k2 = pre + "ffn.fc1", pre + "ffn.fc2"
-                        w1p, b1p = packed(k1, lambda k=k1: (sd[k + ".weight"], sd[k + ".bias"]), dma=True)
-                        ck = (k2, dt, "dma-kperm")
-                        if ck not in wc:
-                            wc[ck] = (pb.pack_weight_dma(sd[k2 + ".weight"], kperm=True), pb.upload(sd[k2 + ".bias"].float()))
-                        w2p, b2p = wc[ck]
+                        w1p, b1p = W.linear([k1], dma=True)
+                        w2p, b2p = W.cached((k2, dt, "dma-kperm"), lambda: (pb.pack_weight_dma(sd[k2 + ".weight"], kperm=True),
+                                                                             pb.upload(sd[k2 + ".bias"].float())))
                         pb.mlp_fused(tokens(hbuf), w1p, b1p, w2p, b2p, tokens(A_), tokens(A_))
                         continue
                     linear(pre + "ffn.fc1", hbuf, ffn, act=L.ACT_GELU, out_split=True)
@@ -666,13 +653,13 @@ class _CaptionPlans(_StepPlans):
         mp = "model.multi_modal_projector."
         h = x.H
         Cv = x.C
-        ck = ("pos2d", h)
-        if ck not in wc:
+
+        def pos_tables():
             col = sd[mp + "image_position_embed.column_embeddings.weight"][:h]
             row = sd[mp + "image_position_embed.row_embeddings.weight"][:h]
             pos = torch.cat([col.unsqueeze(0).repeat(h, 1, 1), row.unsqueeze(1).repeat(1, h, 1)], -1).reshape(h * h, Cv)
-            wc[ck] = (pb.upload(pos.float()), pb.upload(sd[mp + "visual_temporal_embed.pos_idx_to_embed"][0].float()))
-        pos2d, temporal = wc[ck]
+            return pb.upload(pos.float()), pb.upload(sd[mp + "visual_temporal_embed.pos_idx_to_embed"][0].float())
+        pos2d, temporal = W.cached(("pos2d", h), pos_tables)
         pb.keep += [pos2d, temporal]
         n_img = h * h + 1
         self.n_img = n_img
@@ -689,19 +676,12 @@ class _CaptionPlans(_StepPlans):
         lm = "model.language_model."
         S = n_img + len(PROMPT_IDS)
         self.S = S
-        ck = ("prompt", dt)
-        if ck not in wc:
-            emb = sd[lm + "shared.weight"][torch.tensor(PROMPT_IDS)] * w.embed_scale
-            wc[ck] = pb.upload(emb.to(torch_dtype(dt)))
-        txt = wc[ck]
+        txt = W.cached(("prompt", dt), lambda: pb.upload((sd[lm + "shared.weight"][torch.tensor(PROMPT_IDS)] * w.embed_scale).to(torch_dtype(dt))))
         pb.keep.append(txt)
         enc = pb.alloc(B, S, 1, D)
         pb.add_op(L.make_op(L.OP_ASSEMBLE, dt, p=[img_feat.ptr, txt.data_ptr(), None, None, enc.ptr],
                             i={0: B, 1: n_img, 2: len(PROMPT_IDS), 3: D}))
-        ck = ("encpos", S, dt)
-        if ck not in wc:
-            wc[ck] = pb.upload(sd[lm + "encoder.embed_positions.weight"][2:2 + S].to(torch_dtype(dt)))
-        encpos = wc[ck]
+        encpos = W.cached(("encpos", S, dt), lambda: pb.upload(sd[lm + "encoder.embed_positions.weight"][2:2 + S].to(torch_dtype(dt))))
         pb.keep.append(encpos)
         xa = pb.alloc(B, S, 1, D)
         dma_enc = grp["dma"] = use_dma and D % 128 == 0     # every encoder linear (K = D or 4D, N multiple of D) then takes the DMA GEMM
@@ -748,15 +728,7 @@ class _CaptionPlans(_StepPlans):
             return
         # ---------------- decoder step plan (for a single micro-batch; batches of several micro-batches decode through _DecodePlans)
         self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam)
-        if dev.type == "cuda":
-            torch.cuda.synchronize(dev)      # allocations / uploads ran on the current stream: order them before cap.stream
-        if cap.use_graph:
-            self.reset()
-            self.encode_plan.run(cap.stream); self.step_plan.run(cap.stream)
-            cap.stream.synchronize()
-            self.encode_plan.capture(cap.stream)
-            self.step_plan.capture(cap.stream)
-            cap.stream.synchronize()
+        self._warm_up_and_capture(cap, self.encode_plan, self.step_plan)
 
     def rows_for(self, cap: "Florence2Captioner", n: int) -> int:
         """Row count of the graph a micro-batch of n < B crops runs in this plan set's buffers.  Building a twin costs what building a
@@ -829,7 +801,7 @@ class Florence2Captioner:
         self.early_exit_every = 5        # poll the all-rows-finished flag every N decode steps (0 = always run max_new_tokens steps)
         self.num_beams = 1               # caption_crops / ScreenParser: 1 = greedy (the reference's call), k > 1 = beam search
         self.last_steps = 0              # decode steps the last `_run` / `_decode_merged` issued
-        self._lut = None
+        self._lut, self._bic = None, {}  # crop op tables (`_crop_tables`)
         self._lock = L.DeviceLock(self.device, reentrant=True)   # one caption batch at a time per model; makes this GPU the thread's current device
 
     def to(self, *a, **k):
@@ -1033,7 +1005,7 @@ class Florence2Captioner:
             return cp.result_ids(n).clone()
         if cp.beam:                        # finished hypotheses [n, k, T], their scores and generated lengths (synchronises)
             return cp.fin_ids[:n].cpu().long(), cp.fin_score[:n].cpu().clone(), cp.fin_len[:n].cpu().long()
-        return self._finish_ids(cp.ids[:n].cpu().long())     # synchronises the stream
+        return cp.ids[:n].cpu().long()     # synchronises the stream
 
     def _finish_ids(self, ids: torch.Tensor) -> torch.Tensor:
         n = ids.shape[0]
@@ -1066,11 +1038,39 @@ class Florence2Captioner:
         if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= k:
             raise ValueError(f"num_return_sequences must be in 1..num_beams ({k}), got {num_return_sequences!r}")
         with self._lock:
-            if beam is None:
-                seq, scores = self._generate_locked(pixel_values, max_new_tokens), None
-            else:
-                seq, scores = self._generate_beams_locked(pixel_values, max_new_tokens, beam, num_return_sequences)
+            Bn, _, R, R2 = pixel_values.shape
+            assert R == R2
+
+            def fill(cp, s, n):
+                cp.x_in.t[:n, :, :, :3] = pixel_values[s:s + n].to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
+            seq, scores = self._results(self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill), beam,
+                                        num_return_sequences)
         return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
+
+    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill):
+        """encode + decode n_all images in chunks of `chunk` on the captioner's stream, each on the plan of its bucket: fill(cp, s, n)
+        writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  The `_run` result of
+        every chunk, for `_results`."""
+        if src.is_cuda:                                     # pixels / a screenshot the caller is still producing on its own stream
+            self.stream.wait_stream(torch.cuda.current_stream(src.device))
+        parts = []
+        for s in range(0, n_all, chunk):
+            n = min(chunk, n_all - s)
+            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam)
+            with torch.cuda.stream(self.stream):
+                cp.reset()
+                fill(cp, s, n)
+                parts.append(self._run(cp, n, max_new_tokens))
+        return parts
+
+    def _results(self, parts, beam, nrs=1):
+        """(sequences, sequences_scores) of the per-chunk `_run` results: beam search as `_beam_outputs`; greedy decoding (scores
+        None): every chunk trimmed where hf stops (`_finish_ids`), then padded to the longest"""
+        if beam:
+            return self._beam_outputs(parts, nrs)
+        parts = [self._finish_ids(p) for p in parts]
+        T = max(p.shape[1] for p in parts)
+        return torch.cat([torch.nn.functional.pad(p, (0, T - p.shape[1]), value=self.w.pad) for p in parts]), None
 
     def _beam_outputs(self, parts, nrs):
         """hf's output of _beam_search (generation/utils.py:3508-3523) from per-chunk (ids [n,k,T], scores [n,k], lengths [n,k]): the
@@ -1081,44 +1081,6 @@ class Florence2Captioner:
         T = 1 + int(lens.max()) if lens.numel() else 1
         return ids[:, :T].contiguous(), scores
 
-    def _generate_beams_locked(self, pixel_values, max_new_tokens, beam, nrs):
-        Bn, _, R, R2 = pixel_values.shape
-        assert R == R2
-        parts = []
-        for s in range(0, Bn, 128):
-            chunk = pixel_values[s:s + 128]
-            n = chunk.shape[0]
-            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam)
-            if chunk.is_cuda:
-                self.stream.wait_stream(torch.cuda.current_stream(chunk.device))
-            with torch.cuda.stream(self.stream):
-                cp.reset()
-                cp.x_in.t[:n, :, :, :3] = chunk.to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
-                parts.append(self._run(cp, n, max_new_tokens))
-        return self._beam_outputs(parts, nrs)
-
-    def _generate_locked(self, pixel_values, max_new_tokens):
-        Bn, _, R, R2 = pixel_values.shape
-        assert R == R2
-        out = []
-        for s in range(0, Bn, 128):
-            chunk = pixel_values[s:s + 128]
-            n = chunk.shape[0]
-            cp = self.plans(self.bucket(n), R, max_new_tokens)
-            if chunk.is_cuda:                                   # pixel_values the caller is still producing on its own stream
-                self.stream.wait_stream(torch.cuda.current_stream(chunk.device))
-            with torch.cuda.stream(self.stream):
-                cp.reset()
-                cp.x_in.t[:n, :, :, :3] = chunk.to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
-                out.append(self._run(cp, n, max_new_tokens))
-        T = max(o.shape[1] for o in out)
-        res = torch.full((Bn, T), self.w.pad, dtype=torch.long)
-        o0 = 0
-        for o in out:
-            res[o0:o0 + o.shape[0], :o.shape[1]] = o
-            o0 += o.shape[0]
-        return res
-
     @torch.inference_mode()
     def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None):
         """Fused fast path: crops are cut, resized (cv2-bilinear 64x64, then Pillow-bicubic to R on the
@@ -1126,48 +1088,42 @@ class Florence2Captioner:
         num_beams: None = `self.num_beams` (default 1, greedy); k > 1 = beam search, the best hypothesis per crop (what
         generate(num_beams=k) returns for the same pixels)."""
         beam = self.beam_config(num_beams)
-        with self._lock:
-            return self._caption_crops_locked(image_u8, boxes_px, max_new_tokens, batch_size, beam)
+        batch_size = max(1, min(int(batch_size), 128))      # plan capacity: buckets stop at 128 crops (the reference's default batch)
 
-    def _caption_crops_locked(self, image_u8, boxes_px, max_new_tokens, batch_size, beam=None):
-        n_all = len(boxes_px)
-        R = self.resolution
-        outs = []
-        H, W = image_u8.shape[:2]
+        def fill(cp, s, n):
+            rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
+            self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
+        with self._lock:
+            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill)
+        if not parts:
+            return torch.zeros((0, 1), dtype=torch.long)
+        return self._results(parts, beam)[0]
+
+    # ---- device crop pre-processing (OMNI_OP_CROP_RESIZE), shared by caption_crops and ScreenParser
+    def _crop_tables(self, R):
+        """(1/255 LUT of the u8 -> f32 conversion, (bicubic 64 -> R bounds, weights, taps) or (None, None, 0) at R = 64), built on first use"""
         if self._lut is None:
             self._lut = torch.from_numpy((np.arange(256).astype(np.float64) * (1 / 255)).astype(np.float32)).to(self.device)
-            if R != 64:
-                b, k = L.resample_coeffs(64, R, 1)
-                self._bic = (torch.from_numpy(b).to(self.device), torch.from_numpy(k).to(self.device), k.shape[1])
-        batch_size = max(1, min(int(batch_size), 128))      # plan capacity: buckets stop at 128 crops (the reference's default batch)
-        if image_u8.is_cuda:                                 # a screenshot the caller is still uploading / drawing on its own stream
-            self.stream.wait_stream(torch.cuda.current_stream(image_u8.device))
-        for s in range(0, n_all, batch_size):
-            boxes = boxes_px[s:s + batch_size]
-            n = len(boxes)
-            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam)
-            with torch.cuda.stream(self.stream):
-                cp.reset()
-                bx = torch.tensor(boxes, dtype=torch.int32).to(self.device, non_blocking=True)
-                c64 = torch.empty((n, 64, 64, 3), dtype=torch.uint8, device=self.device)
-                tmp = torch.empty((n, 64, R, 3), dtype=torch.uint8, device=self.device) if R != 64 else None
-                bb, kk, ks = self._bic if R != 64 else (None, None, 0)
-                op = L.make_op(L.OP_CROP_RESIZE, self.dtype,
-                               p=[image_u8.data_ptr(), bx.data_ptr(), c64.data_ptr(), tmp.data_ptr() if tmp is not None else None,
-                                  cp.x_in.ptr, bb.data_ptr() if bb is not None else None, kk.data_ptr() if kk is not None else None,
-                                  self._lut.data_ptr()],
-                               i={0: n, 1: H, 2: W, 3: R, 4: ks, 13: cp.x_in.ld},
-                               f={0: CLIP_MEAN[0], 1: CLIP_MEAN[1], 2: CLIP_MEAN[2], 3: CLIP_STD[0], 4: CLIP_STD[1], 5: CLIP_STD[2]})
-                L.launch(op, self.stream)
-                outs.append(self._run(cp, n, max_new_tokens))
-        if not outs:
-            return torch.zeros((0, 1), dtype=torch.long)
-        if beam:
-            return self._beam_outputs(outs, 1)[0]
-        T = max(o.shape[1] for o in outs)
-        res = torch.full((n_all, T), self.w.pad, dtype=torch.long)
-        o0 = 0
-        for o in outs:
-            res[o0:o0 + o.shape[0], :o.shape[1]] = o
-            o0 += o.shape[0]
-        return res
+        if R != 64 and R not in self._bic:
+            b, k = L.resample_coeffs(64, R, 1)
+            self._bic[R] = (torch.from_numpy(b).to(self.device), torch.from_numpy(k).to(self.device), k.shape[1])
+        return self._lut, self._bic.get(R, (None, None, 0))
+
+    def crop_scratch(self, n, R):
+        """device scratch of the crop op for n crops at resolution R: (64x64 crops, 64-row intermediate of the resize to R or None)"""
+        c64 = torch.empty((n, 64, 64, 3), dtype=torch.uint8, device=self.device)
+        return c64, (torch.empty((n, 64, R, 3), dtype=torch.uint8, device=self.device) if R != 64 else None)
+
+    def launch_crops(self, cp, row0, n, image_u8, rects, c64, tmp, stream):
+        """one OMNI_OP_CROP_RESIZE launch on `stream`: the n rectangles `rects` (int32 [n, 4] x0 y0 x1 y1 on the device) of one HWC
+        uint8 frame, cut, resized to cp.R and normalised into rows [row0, row0 + n) of cp.x_in.  c64 / tmp: `crop_scratch` of at
+        least n crops, not reused by other streams before the launch has run."""
+        R, x = cp.R, cp.x_in
+        lut, (bb, kk, ks) = self._crop_tables(R)
+        H, W = image_u8.shape[:2]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        L.launch(L.make_op(L.OP_CROP_RESIZE, self.dtype,
+                           p=[image_u8.data_ptr(), rects.data_ptr(), c64.data_ptr(), ptr(tmp), x.ptr + row0 * R * R * x.ld * x.t.element_size(),
+                              ptr(bb), ptr(kk), lut.data_ptr()],
+                           i={0: n, 1: H, 2: W, 3: R, 4: ks, 13: x.ld},
+                           f={0: CLIP_MEAN[0], 1: CLIP_MEAN[1], 2: CLIP_MEAN[2], 3: CLIP_STD[0], 4: CLIP_STD[1], 5: CLIP_STD[2]}), stream)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .florence import CLIP_MEAN, CLIP_STD, Florence2Captioner
+from .florence import Florence2Captioner
 from .util import utils as U
 from .util.yolov9 import YOLOv9Detector
 
@@ -298,12 +298,6 @@ class ScreenParser:
         else:
             flat = [(fi, b) for fi, cl in enumerate(crops_per_frame) for b in cl]
         ids_all = []
-        if cap._lut is None:
-            cap._lut = torch.from_numpy((np.arange(256).astype(np.float64) * (1 / 255)).astype(np.float32)).to(cap.device)
-            if R != 64:
-                b, k = L.resample_coeffs(64, R, 1)
-                cap._bic = (torch.from_numpy(b).to(cap.device), torch.from_numpy(k).to(cap.device), k.shape[1])
-        esz = 4 if cap.dtype == L.F32 else 2
         # more than one micro-batch: the encode side runs per micro-batch, the 20 decode steps ONCE over all crops
         # (florence.py::_DecodePlans); OMNI_MERGED_DECODE=0 = every micro-batch decodes on its own (A/B knob)
         merged = len(flat) > self.batch_size and os.environ.get("OMNI_MERGED_DECODE", "1") != "0"
@@ -343,9 +337,7 @@ class ScreenParser:
                     stream.wait_event(dec.free_evt)      # the decode two batches ago read this decode plan's cross-attention K/V
                 if not merged:
                     cp.reset()
-                c64 = torch.empty((n, 64, 64, 3), dtype=torch.uint8, device=cap.device)
-                tmp = torch.empty((n, 64, R, 3), dtype=torch.uint8, device=cap.device) if R != 64 else None
-                bb, kk, ks = cap._bic if R != 64 else (None, None, 0)
+                c64, tmp = cap.crop_scratch(n, R)
                 if crops_dev is None:
                     bx = torch.tensor([b for _, b in chunk], dtype=torch.int32).to(cap.device, non_blocking=True)
                 o = 0
@@ -354,16 +346,8 @@ class ScreenParser:
                     e = o
                     while e < n and chunk[e][0] == fi:
                         e += 1
-                    H, W = frames[fi].shape[:2]
                     rects = crops_dev[fi, chunk[o][1]:] if crops_dev is not None else bx[o:]     # rows of one frame are contiguous
-                    op = L.make_op(
-                        L.OP_CROP_RESIZE, cap.dtype,
-                        p=[frames[fi].data_ptr(), rects.data_ptr(), c64[o:].data_ptr(), tmp[o:].data_ptr() if tmp is not None else None,
-                           cp.x_in.ptr + o * R * R * cp.x_in.ld * esz, bb.data_ptr() if bb is not None else None,
-                           kk.data_ptr() if kk is not None else None, cap._lut.data_ptr()],
-                        i={0: e - o, 1: H, 2: W, 3: R, 4: ks, 13: cp.x_in.ld},
-                        f={0: CLIP_MEAN[0], 1: CLIP_MEAN[1], 2: CLIP_MEAN[2], 3: CLIP_STD[0], 4: CLIP_STD[1], 5: CLIP_STD[2]})
-                    L.launch(op, stream)
+                    cap.launch_crops(cp, o, e - o, frames[fi], rects, c64[o:], tmp[o:] if tmp is not None else None, stream)
                     o = e
                 if merged:
                     cap._encode_into(cp, n, dec, s, stream)

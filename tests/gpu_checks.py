@@ -1369,31 +1369,14 @@ def real_crop_boxes(seed, n, iw=1920, ih=1080):
 
 
 def _fill_rows(cap, cp, frame_dev, boxes, rows):
-    """device crop pre-processing (OMNI_OP_CROP_RESIZE) of boxes[i] into row rows[i] of the plan's input tensor."""
-    from omniparser_amd.florence import CLIP_MEAN, CLIP_STD
-    R = cp.R
-    H, W = frame_dev.shape[:2]
-    if cap._lut is None:
-        cap._lut = torch.from_numpy((np.arange(256).astype(np.float64) * (1 / 255)).astype(np.float32)).to(cap.device)
-        if R != 64:
-            b, k = L.resample_coeffs(64, R, 1)
-            cap._bic = (torch.from_numpy(b).to(cap.device), torch.from_numpy(k).to(cap.device), k.shape[1])
-    esz = 4 if cap.dtype == L.F32 else 2
+    """device crop pre-processing (OMNI_OP_CROP_RESIZE) of boxes[i] into row rows[i] of the plan's input tensor, one launch per crop."""
     keep = []
     with torch.cuda.stream(cap.stream):
         for bx_, r in zip(boxes, rows):
             bx = torch.tensor([bx_], dtype=torch.int32).to(cap.device)
-            c64 = torch.empty((1, 64, 64, 3), dtype=torch.uint8, device=cap.device)
-            tmp = torch.empty((1, 64, R, 3), dtype=torch.uint8, device=cap.device) if R != 64 else None
-            bb, kk, ks = cap._bic if R != 64 else (None, None, 0)
-            op = L.make_op(L.OP_CROP_RESIZE, cap.dtype,
-                           p=[frame_dev.data_ptr(), bx.data_ptr(), c64.data_ptr(), tmp.data_ptr() if tmp is not None else None,
-                              cp.x_in.ptr + r * R * R * cp.x_in.ld * esz, bb.data_ptr() if bb is not None else None,
-                              kk.data_ptr() if kk is not None else None, cap._lut.data_ptr()],
-                           i={0: 1, 1: H, 2: W, 3: R, 4: ks, 13: cp.x_in.ld},
-                           f={0: CLIP_MEAN[0], 1: CLIP_MEAN[1], 2: CLIP_MEAN[2], 3: CLIP_STD[0], 4: CLIP_STD[1], 5: CLIP_STD[2]})
-            L.launch(op, cap.stream)
-            keep += [bx, c64, tmp]
+            scratch = cap.crop_scratch(1, cp.R)
+            cap.launch_crops(cp, r, 1, frame_dev, bx, *scratch, cap.stream)
+            keep += [bx, *scratch]
         cap.stream.synchronize()
 
 
