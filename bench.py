@@ -16,12 +16,15 @@ are already resident in HBM as RGB bytes:
 
 W untimed warm-up steps, exactly K timed steps between barrier+synchronize pairs, MAX over ranks, rank 0
 prints ONE JSON line; `value` = screenshots of all ranks / that time.  Screenshots shard across ranks with
-no data-path collective; the only exchange is one all_gather of packed element records per job.
+no data-path collective; the only exchange is one all_gather of packed element records per job.  A plain run does
+that and nothing else (besides --dump-outputs).
 
-Extra objects: `roofline` (dominant kernel family = the GEMMs: algorithmic conv/linear FLOPs per step at the REAL
-crop count / HIP-event time of exactly those launches timed in sequence, vs the dense f16 MFMA peak), `extra`
-(N=1: BASELINE configs[1] detector-only at both network sizes, the 64x64 crop size, configs[4] tiled 4K) and
-`cpu_baseline` (the reference-equivalent CPU path from oracle/, timed on rank 0 at N=1 on a bounded sample).
+--full adds, after the timed region: `roofline` (dominant kernel family = the GEMMs: algorithmic conv/linear FLOPs per
+step at the REAL crop count / HIP-event time of exactly those launches timed in sequence, vs the dense f16 MFMA peak),
+`extra` (N=1: BASELINE configs[1] detector-only at both network sizes, the 64x64 crop size, configs[4] tiled 4K, and
+unless --no-ab the child-process lines), `cpu_baseline` (the reference-equivalent CPU path from oracle/, timed on rank 0
+at N=1 on a bounded sample) and `config.parity_scan` (the committed record of the GPU-vs-oracle scan, quoted while it
+still describes this tree).  --no-extra and --no-cpu-baseline trim a --full run.
 Weights are seeded-random (tools/make_weights.py); data is synthetic (omniparser_amd/synth.py).
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the timed path returned in its last step as DIR/<name>.npy (float32 /
@@ -49,10 +52,12 @@ def parse_args():
     ap.add_argument("--precision", default=os.environ.get("OMNI_PRECISION", "f32"), choices=["f32", "f16"])
     ap.add_argument("--caption-res", type=int, default=768, choices=[64, 768])
     ap.add_argument("--imgsz", default="640", help="'640' (reference default) or 'native' (1088x1920 network input)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline figure does not need: "
+                    "`roofline`, `extra`, `cpu_baseline`, `config.parity_scan`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--micro-batch", type=int, default=int(os.environ.get("OMNI_CAPTION_MICRO_BATCH", "128")), choices=[32, 64, 96, 128],
                     help="crops per caption micro-batch (plan capacity; the reference's batch_size = 128, ref:util/utils.py:89)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the `extra` object (configs[1], 64x64 crops, tiled 4K)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the `extra` object (configs[1], 64x64 crops, tiled 4K)")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false",
                     help="time K synchronous parse_batch calls instead of the K steps through ScreenParser.parse_stream (the default: "
                          "detector of step i+1, two encode lanes and the decode of step i overlap; same kernels, same results)")
@@ -60,7 +65,7 @@ def parse_args():
     ap.set_defaults(pipeline=True)
     ap.add_argument("--lanes", type=int, default=2, choices=[1, 2, 3, 4], help="with --pipeline: caption micro-batches in flight at once (HIP streams); "
                     "3 / 4: experiments (each lane holds its own 128-row encode plans, ~25 GB each at 768x768 crops)")
-    ap.add_argument("--no-ab", action="store_true", help="skip the child-process measurements (`extra.e2e_r64_f16_reference_cuda_branch`, `extra.annotate_tail`, `extra.stream_*`)")
+    ap.add_argument("--no-ab", action="store_true", help="with --full: skip the child-process measurements (`extra.e2e_r64_f16_reference_cuda_branch`, `extra.annotate_tail`, `extra.stream_*`)")
     ap.add_argument("--width", type=float, default=1.0, help="debug only: detector channel multiplier (1.0 = YOLOv9-E)")
     ap.add_argument("--frame", default="1920x1080", help="debug only: synthetic frame size WxH (the metric is quoted on 1920x1080; the CPU test "
                     "of the N > 1 path runs a small frame on the host emulation)")
@@ -282,7 +287,7 @@ def main():
         out["config"]["decode"] = ("one 20-step decode over all crops of the batch (cross-attention K/V of every micro-batch copied into one plan)"
                                    if os.environ.get("OMNI_MERGED_DECODE", "1") != "0" else "per micro-batch")
         out["config"]["text"] = "caption ids -> strings (tokenizers batch_decode + strip, ref:util/utils.py:128-130) inside the timed region (pipeline.py::caption_finish)"
-        out["config"]["frames"] = "8 device-resident frames reused every step (inputs in HBM when the timed region starts); extra.e2e_pcie_inclusive uploads them per step"
+        out["config"]["frames"] = "8 device-resident frames reused every step (inputs in HBM when the timed region starts); --full's extra.e2e_pcie_inclusive uploads them per step"
         out["config"]["hand_off"] = "device (detector + hand-off ops in one hipGraph)" if getattr(parser, "device_glue", False) else "host"
     # parity of the benched composition on frames the stand-in's calibration never saw — quoted from the committed record of the measured
     # scan (tools/scan_gpu_vs_oracle.py: the oracle's final lists computed in the CPU container, the detector + hand-off on the MI355X), not
@@ -291,7 +296,7 @@ def main():
     # order in which 84 conv shapes sum their K partials) and same kernel sources (round 5 quoted a scan measured before
     # the tuning table existed).
     scans = sorted((ROOT / "profiles").glob("r*_scan_gpu_vs_oracle.json"), key=lambda p: [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", p.name)])
-    if args.mode == "e2e" and scans:
+    if args.full and args.mode == "e2e" and scans:
         try:
             import hashlib
             scan = scans[-1]
@@ -328,9 +333,10 @@ def main():
                 import traceback
                 traceback.print_exc(file=sys.stderr)
                 out[name] = {"error": f"{type(e).__name__}: {e}"[:400]}
-        dp_obj = dp if args.mode == "detect" else None
-        guarded("roofline", lambda: roofline(args, det, parser, dp_obj, crop_counts, B))
-        if world == 1 and not args.no_extra:
+        if args.full:
+            dp_obj = dp if args.mode == "detect" else None
+            guarded("roofline", lambda: roofline(args, det, parser, dp_obj, crop_counts, B))
+        if args.full and world == 1 and not args.no_extra:
             guarded("extra", lambda: extras(args, det, parser, frames, ocr, dev, cap_dir))
         if world == 1 and not args.no_extra and not args.no_ab and args.mode == "e2e" and isinstance(out.get("extra"), dict):
             # this process is done with the GPU: give its activation pools back before the children build their own plans
@@ -344,8 +350,8 @@ def main():
             # pipeline, f16 plans.  Not the parity mode: its parity class is a token-match RATE against the fp32 oracle
             # (tests/test_gpu_b_caption_model.py::test_captioner_f16_token_match_rate_r64), not exactness.  Own process, hard limit.
             out["extra"]["e2e_r64_f16_reference_cuda_branch"] = child_json(
-                [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--no-extra", "--no-cpu-baseline", "--caption-res", "64",
-                 "--precision", "f16"], {}, 150,
+                [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--full", "--no-extra", "--no-cpu-baseline",
+                 "--caption-res", "64", "--precision", "f16"], {}, 150,
                 keep=("value", "ms_per_step", "steps", "dtype", ("config", "workload"), ("config", "mean_crops_per_screenshot"),
                       ("roofline", "gemm_ms_per_step"), ("roofline", "achieved")))
             note("e2e_r64_f16 done")
@@ -364,7 +370,7 @@ def main():
                 [sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "stream_bench.py"), "--items", "24",
                  "--caption-res", "768"], {}, 240, keep=keep)
             note("stream_mixed_resolution_r768 done")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             guarded("cpu_baseline", lambda: cpu_baseline(args, blob, imgsz, out["config"].get("mean_crops_per_screenshot", 0)))
         faulthandler.cancel_dump_traceback_later()
         print(json.dumps(out), flush=True)
@@ -399,7 +405,7 @@ _GENERATE = ("import sys; from pathlib import Path; sys.path.insert(0, sys.argv[
 
 
 def standin_checkpoints(args, rank, world):
-    """(detector blob, caption checkpoint dir) of the seeded stand-ins, generated on first use by rank 0 in a child process.  They live
+    """(detector blob, caption checkpoint dir) of the seeded stand-ins, generated on first use by rank 0 in child processes.  They live
     in <repo>/weights when that directory already holds them or can be written; in a read-only checkout, in a per-user cache
     ($XDG_CACHE_HOME or ~/.cache, else the temp directory).  Same seeds and committed calibration: the same weights either way.
     OMNI_WEIGHTS_DIR is set to the choice for the child processes of this script."""
@@ -425,12 +431,15 @@ def standin_checkpoints(args, rank, world):
             raise RuntimeError("no writable directory for the stand-in checkpoints")
     os.environ["OMNI_WEIGHTS_DIR"] = str(wdir)
     if rank == 0:
-        for kind, marker in kinds.items():
-            if not (wdir / marker).exists():
-                cmd = [sys.executable, "-c", _GENERATE, str(Path(MW.__file__).resolve().parents[1]), str(wdir), kind, str(args.width)]
-                r = subprocess.run(cmd, capture_output=True, text=True)
-                if r.returncode != 0 or not (wdir / marker).exists():
-                    raise RuntimeError(f"stand-in {kind} generation failed in {wdir}:\n{r.stderr[-2000:]}")
+        # one child per missing kind, side by side: seeded initialisation is serial work, so a first run waits for the slower
+        # child instead of both; every child has ended before any failure is raised
+        procs = {kind: subprocess.Popen([sys.executable, "-c", _GENERATE, str(Path(MW.__file__).resolve().parents[1]), str(wdir), kind,
+                                         str(args.width)], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+                 for kind, marker in kinds.items() if not (wdir / marker).exists()}
+        errs = {kind: p.communicate()[1] for kind, p in procs.items()}
+        for kind, p in procs.items():
+            if p.returncode != 0 or not (wdir / kinds[kind]).exists():
+                raise RuntimeError(f"stand-in {kind} generation failed in {wdir}:\n{errs[kind][-2000:]}")
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
