@@ -152,7 +152,10 @@ enum {
    *  i0 ldq i1 ldk i2 ldv i3 ldo i4 qoff i5 koff i6 voff i7 ooff i8 heads i9 nq i10 nk i11 groups
    *  i12 mode i13 H i14 W i15 head_dim (32|64); f0 scale
    *  i16 = 1 (f32 plans, MFMA kernels): write o in format B (see OMNI_OP_CONV i20 = 2) for the LDS-DMA GEMM that follows
-   *  f32 plans, MFMA kernels (mode 1 with head_dim 32, mode 0 with head_dim 64): row pitches and channel offsets % 4 == 0 */
+   *  f32 plans, MFMA kernels (mode 1 with head_dim 32, mode 0 with head_dim 64): row pitches and channel offsets % 4 == 0
+   *  Ragged prompts (additive; NULL = all nk keys): p7 valid keys per group i32[groups], mode 0 only.  Group g attends to its first
+   *  p7[g] keys (clamped to 1..nk); its rows still lie nk apart, so rows at or beyond the count exist and are only read as
+   *  queries: they are computed over the valid keys, stay finite, and nobody reads them as keys. */
   OMNI_OP_ATTN_ROWS = 10,
   /* DaViT grouped channel attention (florence2 :223-259): p0 qkv [B*N,3C] p4 o [B*N,C] p5 ws f32[B*G*chunks*1024]
    *  i0 B i1 N i3 C i4 G i5 chunk_tokens i6 = 1: o in format B (f32 plans); f0 scale (0 => N^-0.5) */
@@ -161,7 +164,10 @@ enum {
    *  i0 B i1 N i3 C */
   OMNI_OP_PROJ_PREP = 12,
   /* encoder input = [image features ; prompt embeddings] (florence2 :933-960): p0 img [B,n_img,C] p1 txt [n_txt,C] p4 y
-   *  i0 B i1 n_img i2 n_txt i3 C */
+   *  i0 B i1 n_img i2 n_txt i3 C
+   *  Prompt as a plan input (additive; p2 NULL = the constant block p1): p2 ids i32[B,n_txt] p3 token table [i4, C] (plan dtype),
+   *  p1 NULL; y[b][n_img + t] = table[ids[b][t]] * f0 (0 => 1).  Positions behind a row's prompt hold the pad token.  The caller
+   *  checks 0 <= id < i4 before it writes the ids; the kernel clamps. */
   OMNI_OP_ASSEMBLE = 13,
   /* decoder token embedding + learned position (bart :80-98): y[b] = table[ids[b][step]]*scale + pos[step+off]
    *  p0 table p1 pos p2 ids i32[B,T] p4 y [B,C] p6 step i32*; i0 B i3 C i4 T i5 pos offset; f0 scale */
@@ -171,7 +177,9 @@ enum {
    *  i0 ldq i1 qoff i2 ldn i3 koff i4 voff i5 ldo i6 heads i7 nk_fixed i8 cap i9 C i10 B i11 cache row stride (0 => C); f0 scale
    *  Beam plans (additive; NULL / 0 = the behaviour above): p7 self-attention position table i32 [B, cap], entry [b][t] = the
    *  cache row that holds position t of row b (row b still appends its own k / v at (b, step)); i12 cross-attention rows per
-   *  cache row: row b reads kcache / vcache row b / i12 (the k beams of a crop share its one cross-K / V row) */
+   *  cache row: row b reads kcache / vcache row b / i12 (the k beams of a crop share its one cross-K / V row)
+   *  Ragged prompts (additive; NULL = nk_fixed keys everywhere): in cross-attention (i7 > 0, which needs i7 <= i8) p7 is the
+   *  number of valid keys per cache row, i32[ceil(B / i12)], read at b / i12 and clamped to 1..nk_fixed */
   OMNI_OP_ATTN_DECODE = 15,
   /* greedy decoding step (hf:generation/utils.py:2783-2937 + logits_process NoRepeatNGram/ForcedBOS/ForcedEOS):
    *  p0 logits [B,ldl] p1 final_logits_bias f32 or NULL p2 ids i32[B,T] p3 finished i32[B] p6 step i32*

@@ -86,7 +86,7 @@ static int dispatch(const omni_op_t* op, hipStream_t s) {
 // (hipMemGetAddressRange; with a caching allocator the allocation is the allocator's segment — a wild pointer or a range that
 // runs off the segment is caught, a neighbour inside the same segment is not).  Ranges are computed for the op kinds that hold
 // almost all of a plan's launches (conv / GEMM family, pools / resizes, LayerNorm, depthwise conv, split-convert, fused FFN,
-// detect-decode, NMS); for the other kinds (attention, decode step, crop, hand-off, PNG) the first byte is checked.  On by default wherever a device is present — omni_op_launch (the single-op path is
+// detect-decode, NMS, the encoder-input assembly, the index tables of the attention ops); for the other kinds (attention data, decode step, crop, hand-off, PNG) the first byte is checked.  On by default wherever a device is present — omni_op_launch (the single-op path is
 // never hot) and omni_plan_create (once per plan) — OMNI_CHECK_PTRS=0 turns it off; without a device there is nothing to check against.
 static bool check_ptrs_enabled() {
   const char* e = getenv("OMNI_CHECK_PTRS");
@@ -173,6 +173,19 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       if (op->kind == OMNI_OP_DWCONV3_LN) { ext[3] = n; ext[5] = C * 4; ext[6] = C * 4; }
       break;
     }
+    case OMNI_OP_ASSEMBLE: {
+      // p0 img [B,n_img,C] p1 txt [n_txt,C] | p2 ids i32[B,n_txt] + p3 table [vocab,C]; p4 y [B,n_img+n_txt,C]
+      const long long B = i[0], n_img = i[1], n_txt = i[2], C = i[3];
+      ext[0] = B * n_img * C * esz; ext[1] = n_txt * C * esz; ext[2] = B * n_txt * 4; ext[3] = (long long)i[4] * C * esz;
+      ext[4] = B * (n_img + n_txt) * C * esz;
+      break;
+    }
+    case OMNI_OP_ATTN_ROWS:                                  // p7: valid keys per group (mode 0); the other pointers: first byte
+      ext[7] = (long long)i[11] * 4;
+      break;
+    case OMNI_OP_ATTN_DECODE:                                // p7: position table [B, cap] (self) or valid keys per cache row (cross)
+      ext[7] = i[7] > 0 ? (long long)((i[10] + (i[12] > 1 ? i[12] : 1) - 1) / (i[12] > 1 ? i[12] : 1)) * 4 : (long long)i[10] * i[8] * 4;
+      break;
     default: break;
   }
   for (int k = 0; k < 8; ++k) if (ext[k] < 1) ext[k] = 1;

@@ -533,7 +533,15 @@ struct AttnArgs {
   int mode, H, W, wy, wx;                            // window mode: image H x W, wy x wx windows of 12x12
   float scale;
   int osplit;                                        // f32 plans: write o in "format B" (hi|lo f16 pairs) for the LDS-DMA GEMM that follows
+  const int* nkeys;                                  // mode 0, or NULL: i32[groups] valid keys per group (<= nk; rows stay nk apart)
 };
+
+// Keys a group attends to (mode 0): nk, or its entry of the per-group table clamped to 1..nk.  The group's rows exist up to nk (the
+// plan's capacity), so every address below nk is in bounds; keys at or beyond the count get no weight (score -inf before the softmax,
+// as transformers' additive finfo.min mask) and key tiles wholly beyond it are not visited.  Uniform over the workgroup.
+__device__ __forceinline__ int attn_valid_keys(const AttnArgs& a, int g) {
+  return a.nkeys ? min(max(a.nkeys[g], 1), a.nk) : a.nk;
+}
 
 // store one f32 output element of channel c of row `row` (f32 elements per row: ld): plain, or as the two halves of format B
 template <typename T>
@@ -573,13 +581,14 @@ __global__ __launch_bounds__(NT) void attn_rows_kernel(AttnArgs a) {
 #pragma unroll
   for (int d = 0; d < D; ++d) { q[d] = qrow >= 0 ? ldf(Q + qrow * a.ldq + a.qoff + h * D + d) : 0.0f; o[d] = 0.0f; }
   float m = -INFINITY, l = 0.0f;
-  for (int k0 = 0; k0 < a.nk; k0 += KT) {
+  const int nkv = attn_valid_keys(a, g);
+  for (int k0 = 0; k0 < nkv; k0 += KT) {
     __syncthreads();
     for (int e = threadIdx.x; e < KT * (D / 4); e += NT) {     // one 4-float group per lane
       int kk = e / (D / 4), d = (e - kk * (D / 4)) * 4;
       int ki = k0 + kk;
       float kq[4] = {0.f, 0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f};
-      if (ki < a.nk) {
+      if (ki < nkv) {
         long long krow = a.mode == 1 ? window_row(a, g, ki) : (long long)g * a.nk + ki;
         if (krow >= 0) {
           const T* kp = K + krow * a.ldk + a.koff + h * D + d;
@@ -598,7 +607,7 @@ __global__ __launch_bounds__(NT) void attn_rows_kernel(AttnArgs a) {
       for (int u = 0; u < 4; ++u) { sk[kk][d + u] = kq[u]; sv[kk][d + u] = vq[u]; }
     }
     __syncthreads();
-    int lim = a.nk - k0 < KT ? a.nk - k0 : KT;
+    int lim = nkv - k0 < KT ? nkv - k0 : KT;
     // online softmax in chunks of 8 keys: one running-max update / accumulator rescale per chunk
     for (int kk0 = 0; kk0 < lim; kk0 += 8) {
       float sc[8];
@@ -1087,13 +1096,14 @@ __global__ __launch_bounds__(256, 2) void mha_mfma_kernel(AttnArgs a) {
     for (int dt = 0; dt < 4; ++dt) { oM[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; oC[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
   }
 
-  for (int k0 = 0; k0 < a.nk; k0 += KB) {
+  const int nkv = attn_valid_keys(a, g);
+  for (int k0 = 0; k0 < nkv; k0 += KB) {
     __syncthreads();
     // ---- stage 32 keys: K row-major, V transposed, hi|lo halves
     for (int e = tid; e < KB * (D / 4); e += 256) {
       int key = e / (D / 4), d0 = (e - key * (D / 4)) * 4;
       float kv[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (k0 + key < a.nk) {
+      if (k0 + key < nkv) {
         long long row = (long long)g * a.nk + k0 + key;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -1136,7 +1146,7 @@ __global__ __launch_bounds__(256, 2) void mha_mfma_kernel(AttnArgs a) {
         for (int r = 0; r < 4; ++r) {
           int key = k0 + kt * 16 + grp * 4 + r;
           float sv = (accM[r] + accC[r] * inv2048) * a.scale;
-          sv = key < a.nk ? sv : -INFINITY;
+          sv = key < nkv ? sv : -INFINITY;
           sc[kt * 4 + r] = sv;
           bm = fmaxf(bm, sv);
         }
@@ -1228,17 +1238,18 @@ __global__ __launch_bounds__(256, 2) void mha_mfma_f32_kernel(AttnArgs a) {
 
   // ---- staging roles: K items (key = t16 + 16 j, channels d0..d0+3), j = 0..3; one V item (keys 4 t16 .. 4 t16 + 3, channels d0..d0+3)
   const int t16 = tid >> 4, d0 = (tid & 15) * 4;
+  const int nkv = attn_valid_keys(a, g);
   f32x4 kraw[4], vraw[4];
   auto load_block = [&](int k0) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int key = k0 + t16 + 16 * j;
-      kraw[j] = key < a.nk ? *reinterpret_cast<const f32x4*>(Kb + key * a.ldk + d0) : z4;
+      kraw[j] = key < nkv ? *reinterpret_cast<const f32x4*>(Kb + key * a.ldk + d0) : z4;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int key = k0 + 4 * t16 + u;
-      vraw[u] = key < a.nk ? *reinterpret_cast<const f32x4*>(Vb + key * a.ldv + d0) : z4;
+      vraw[u] = key < nkv ? *reinterpret_cast<const f32x4*>(Vb + key * a.ldv + d0) : z4;
     }
   };
   auto store_block = [&](unsigned char* st) {
@@ -1287,14 +1298,14 @@ __global__ __launch_bounds__(256, 2) void mha_mfma_f32_kernel(AttnArgs a) {
 
   store_block(lds);
   __syncthreads();
-  const int nblk = (a.nk + KB - 1) / KB;
+  const int nblk = (nkv + KB - 1) / KB;
   for (int ib = 0; ib < nblk; ++ib) {
     const int k0 = ib * KB;
     unsigned char* st = lds + (ib & 1) * STAGE;
     if (ib + 1 < nblk) load_block(k0 + KB);           // in flight under this block's arithmetic
     const unsigned char* Kh = st;
     const unsigned char* Vh = st + 2 * KB * KROW;
-    const bool tail = k0 + KB > a.nk;                 // uniform: only the last block can hold keys >= nk
+    const bool tail = k0 + KB > nkv;                  // uniform: only the last block can hold keys >= the group's key count
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       // ---- S^T[key][query] for 32 keys: lane holds keys kt * 32 + (r & 3) + 8 (r >> 2) + 4 kg of query col
@@ -1313,11 +1324,11 @@ __global__ __launch_bounds__(256, 2) void mha_mfma_f32_kernel(AttnArgs a) {
       f32x2 sc[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) sc[e] = f32x2{accC[2 * e], accC[2 * e + 1]} * inv2048 + f32x2{accM[2 * e], accM[2 * e + 1]};
-      if (tail) {                                     // keys >= nk: -inf added (an addition, not a select: the result stays a canonical number
+      if (tail) {                                     // keys >= the count: -inf added (an addition, not a select: the result stays a canonical number
 #pragma unroll                                        // for the maxima below)
         for (int e = 0; e < 8; ++e) {
           const int key = k0 + kt * 32 + ((2 * e) & 3) + 8 * (e >> 1) + 4 * kg;
-          sc[e] += f32x2{key >= a.nk ? -INFINITY : 0.f, key + 1 >= a.nk ? -INFINITY : 0.f};
+          sc[e] += f32x2{key >= nkv ? -INFINITY : 0.f, key + 1 >= nkv ? -INFINITY : 0.f};
         }
       }
       float bm = fmaxf(sc[0][0], sc[0][1]);
@@ -1670,7 +1681,10 @@ __global__ __launch_bounds__(256) void proj_prep_kernel(PrepArgs a) {
   stf(y, s / (float)a.N);
 }
 
-struct AsmArgs { const void* img; const void* txt; void* y; int B, n_img, n_txt, C; };
+struct AsmArgs {
+  const void* img; const void* txt; void* y; int B, n_img, n_txt, C;
+  const void* table; const int* ids; int vocab; float scale;   // ids != NULL: text rows gathered from the token table [vocab, C]
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void assemble_kernel(AsmArgs a) {
@@ -1681,6 +1695,16 @@ __global__ __launch_bounds__(256) void assemble_kernel(AsmArgs a) {
   long long r = idx / a.C;
   int t = (int)(r % (a.n_img + a.n_txt));
   long long b = r / (a.n_img + a.n_txt);
+  if (a.ids && t >= a.n_img) {
+    // y[b][n_img + t'] = table[ids[b][t']] * scale: the prompt is a plan input, one row of ids per image (padded positions hold the
+    // pad token, whose embedding transformers puts there too).  The host refuses ids outside the table; the clamp keeps a buffer
+    // that was never written from becoming an address.
+    const int tok = min(max(a.ids[b * a.n_txt + (t - a.n_img)], 0), a.vocab - 1);
+    float v = ldf((const T*)a.table + (long long)tok * a.C + c);
+    if (a.scale != 1.0f) v *= a.scale;
+    stf((T*)a.y + idx, v);
+    return;
+  }
   const T* src = t < a.n_img ? (const T*)a.img + (b * a.n_img + t) * a.C + c : (const T*)a.txt + (long long)(t - a.n_img) * a.C + c;
   ((T*)a.y)[idx] = *src;
 }
@@ -1706,7 +1730,13 @@ struct DecArgs {
   int ldq, qoff, ldn, koff, voff, ldo;    // q [B, ldq]; new k/v rows in [B, ldn]
   int heads, nk_fixed, cap, C, ldc;       // cache [B, cap, ldc]; nk_fixed > 0 => cross attention over nk_fixed keys
   float scale;
+  const int* nkeys;                       // cross attention, or NULL: i32 valid keys per cache row (<= nk_fixed), in place of nk_fixed
 };
+
+// keys of cache row bkv in cross attention: nk_fixed, or the row's entry of the table clamped to 1..nk_fixed (uniform over the workgroup)
+__device__ __forceinline__ int decode_cross_keys(const DecArgs& a, int bkv) {
+  return a.nkeys ? min(max(a.nkeys[bkv], 1), a.nk_fixed) : a.nk_fixed;
+}
 
 // Beam plans (BEAM = true, its own instantiation: the kernels of greedy plans are compiled from BEAM = false and stay as they were):
 // self-attention reads position t of row b from cache row table[b][t] (the rows of a crop's beams share the history they have in
@@ -1731,7 +1761,7 @@ __device__ __forceinline__ void attn_decode_body(DecArgs a, const int* table, in
     return (long long)k * C;
   };
   if (a.nk_fixed > 0) {
-    nk = a.nk_fixed;
+    nk = decode_cross_keys(a, bkv);
   } else {
     int st = *a.step;
     nk = st + 1;
@@ -1787,7 +1817,7 @@ __global__ __launch_bounds__(256) void attn_decode_cross_kernel(DecArgs a, int k
   const int bkv = BEAM ? b / kv_div : b;      // beam plans: the k rows of a crop read its one cross-K / V row
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane >> 4, d4 = (lane & 15) * 4;
-  const int nk = a.nk_fixed, C = a.ldc;
+  const int nk = decode_cross_keys(a, bkv), C = a.ldc;
   float* red = sp + ((nk + 3) & ~3);
   float* part = red + 8;
   const float* __restrict__ Kc = (const float*)a.kc + (long long)bkv * a.cap * C + h * 64 + d4;
@@ -2335,7 +2365,9 @@ static int launch_attn_rows(const omni_op_t* op, hipStream_t s) {
   int D = op->i[15];
   a.scale = op->f[0];
   a.osplit = op->i[16];
+  a.nkeys = (const int*)op->p[7];
   OMNI_REQUIRE(a.q && a.k && a.v && a.o && a.heads > 0 && a.nq > 0 && a.nk > 0 && a.groups > 0, "attn_rows: bad arguments");
+  OMNI_REQUIRE(!a.nkeys || a.mode == 0, "attn_rows: the per-group key count (p7) is for mode 0");
   OMNI_REQUIRE(!a.osplit || (op->dtype == OMNI_F32 && a.ldo % 16 == 0 && a.ooff % 16 == 0), "attn_rows: split output needs an f32 plan, 16-channel aligned");
   OMNI_REQUIRE(D == 32 || D == 64, "attn_rows: head_dim %d unsupported", D);
   if (a.mode == 1) {
@@ -2411,10 +2443,12 @@ static int launch_attn_decode(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE(a.q && a.kc && a.vc && a.o && B > 0 && a.heads > 0 && a.C == a.heads * 64, "attn_decode: bad arguments (head_dim 64)");
   OMNI_REQUIRE(a.nk_fixed > 0 || (a.knew && a.vnew && a.step), "attn_decode: self-attention needs new k/v and the step counter");
   // beam plans: p7 = self-attention position table i32 [B, cap], i12 = rows per cross-K / V row (0 / 1 and NULL = one row each)
-  const int* table = (const int*)op->p[7];
+  // p7 in cross-attention: valid keys per cache row i32 [B / i12] (a prompt shorter than the plan's text capacity), NULL = nk_fixed
+  const int* table = a.nk_fixed > 0 ? nullptr : (const int*)op->p[7];
+  a.nkeys = a.nk_fixed > 0 ? (const int*)op->p[7] : nullptr;
   const int kv_div = op->i[12] > 1 ? op->i[12] : 1;
   const bool beam = table != nullptr || kv_div > 1;
-  OMNI_REQUIRE(!table || a.nk_fixed <= 0, "attn_decode: the position table is for self-attention");
+  OMNI_REQUIRE(a.nk_fixed <= 0 || a.nk_fixed <= a.cap, "attn_decode: nk_fixed beyond the cache rows");
   OMNI_REQUIRE(kv_div == 1 || a.nk_fixed > 0, "attn_decode: rows per K/V row > 1 is for cross-attention");
   int nk_max = a.nk_fixed > 0 ? a.nk_fixed : a.cap;
   if (a.nk_fixed > 0 && op->dtype == OMNI_F32 && a.ldc % 4 == 0 && a.ldq % 4 == 0 && a.qoff % 4 == 0) {
@@ -2509,7 +2543,10 @@ static int launch_glue(const omni_op_t* op, hipStream_t s) {
         [&] { hipLaunchKernelGGL(proj_prep_kernel<half_t>, g, dim3(256), 0, s, a); });
   } else if (op->kind == OMNI_OP_ASSEMBLE) {
     AsmArgs a{}; a.img = op->p[0]; a.txt = op->p[1]; a.y = op->p[4]; a.B = op->i[0]; a.n_img = op->i[1]; a.n_txt = op->i[2]; a.C = op->i[3];
-    OMNI_REQUIRE(a.img && a.txt && a.y && a.B > 0 && a.n_img > 0 && a.n_txt >= 0 && a.C > 0, "assemble: bad arguments");
+    a.ids = (const int*)op->p[2]; a.table = op->p[3]; a.vocab = op->i[4]; a.scale = op->f[0] == 0.0f ? 1.0f : op->f[0];
+    OMNI_REQUIRE(a.img && a.y && a.B > 0 && a.n_img > 0 && a.n_txt >= 0 && a.C > 0, "assemble: bad arguments");
+    if (a.ids) OMNI_REQUIRE(a.table && a.vocab > 0 && !a.txt, "assemble: a prompt given as ids (p2) needs the token table (p3, i4 rows) and no constant block (p1)");
+    else OMNI_REQUIRE(a.txt && !a.table, "assemble: the constant text block (p1), or ids (p2) with the token table (p3)");
     long long total = (long long)a.B * (a.n_img + a.n_txt) * a.C;
     dim3 g((unsigned)((total + 255) / 256));
     rc = by_dtype(op->dtype, "assemble",

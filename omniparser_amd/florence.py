@@ -20,6 +20,21 @@ from . import _lib as L
 from .planner import PlanBuilder, View, torch_dtype
 
 PROMPT_IDS = [0, 2264, 473, 5, 2274, 6190, 116, 2]   # <s>What does the image describe?</s>  
+# Text capacities of a plan whose prompt is an INPUT (ids + per-row key counts, see `_CaptionPlans`): a prompt runs on the smallest
+# capacity that holds it.  The ladder is short on purpose: every capacity is one more set of resident plans (several GB each at
+# 768x768 crops), and the encoder computes the padded positions.  The default prompt needs none of this (capacity 8, a constant block).
+TEXT_CAPACITIES = (8, 16, 32, 64)
+
+
+def text_capacity(n_tokens: int) -> int:
+    """smallest text capacity of a plan that holds a prompt of n_tokens ids; more than 64 tokens is a ValueError"""
+    for c in TEXT_CAPACITIES:
+        if n_tokens <= c:
+            return c
+    raise ValueError(f"a prompt of {n_tokens} tokens exceeds the captioner's limit of {TEXT_CAPACITIES[-1]} prompt tokens "
+                     "(bos and eos included)")
+
+
 _BUCKETS = tuple(sorted({min(max(int(x), 1), 128) for x in os.environ.get("OMNI_CAPTION_BUCKETS", "8,16,32,64,96,128").split(",")} | {128}))
 CLIP_MEAN = (0.485, 0.456, 0.406)
 CLIP_STD = (0.229, 0.224, 0.225)
@@ -281,6 +296,12 @@ class _Weights:
     def f32(self, key):
         return self.cached((key, "f32"), lambda: self.pb.upload(self.sd[key].float()))
 
+    def token_tables(self):
+        """(token embedding table, decoder position table) in the plan dtype: the decoder step and the prompt gather read the first"""
+        lm, tdt = "model.language_model.", torch_dtype(self.dt)
+        return self.cached(("dectab", self.dt), lambda: (self.pb.upload(self.sd[lm + "shared.weight"].to(tdt)),
+                                                         self.pb.upload(self.sd[lm + "decoder.embed_positions.weight"].to(tdt))))
+
     def dwconv(self, key):
         """depthwise 3x3 convolution: weight [C,1,3,3] -> [3][3][C] in the plan dtype, f32 bias"""
         wt, b = self.sd[key + ".weight"], self.sd[key + ".bias"]
@@ -304,7 +325,9 @@ class _StepPlans:
     builds the greedy plan, op for op as before."""
     beam = None
 
-    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None):
+    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None):
+        """nkeys: i32 [crops] valid encoder keys per crop (a prompt shorter than the plan's text capacity: OMNI_OP_ATTN_DECODE p7 of
+        the cross-attention), or None = all S"""
         w, dev, dt = cap.w, cap.device, cap.dtype
         sd = w.sd
         D, nh, lm = w.d_model, w.n_heads, "model.language_model."
@@ -341,8 +364,7 @@ class _StepPlans:
         def dln(key, xin: View, out: View):
             pd_.add_op(W.layernorm(key, xin.ptr, out.ptr, B, D))
 
-        table, dpos = W.cached(("dectab", dt), lambda: (W.pb.upload(sd[lm + "shared.weight"].to(torch_dtype(dt))),
-                                                        W.pb.upload(sd[lm + "decoder.embed_positions.weight"].to(torch_dtype(dt)))))
+        table, dpos = W.token_tables()
         pd_.keep += [table, dpos]
         e = pd_.alloc(B, 1, 1, D)
         pd_.add_op(L.make_op(L.OP_EMBED_STEP, dt, p=[table.data_ptr(), dpos.data_ptr(), self.ids.data_ptr(), None, e.ptr,
@@ -370,7 +392,8 @@ class _StepPlans:
             dlinear(pre + "encoder_attn.q_proj", xd, dq)
             kv = self.cross_kv[l]
             pd_.add_op(L.make_op(L.OP_ATTN_DECODE, dt,
-                                 p=[dq.ptr, None, None, kv.ptr, da.ptr, kv.ptr + D * esz, None],
+                                 p=[dq.ptr, None, None, kv.ptr, da.ptr, kv.ptr + D * esz, None]
+                                 + ([nkeys.data_ptr()] if nkeys is not None else []),
                                  i={0: D, 1: 0, 2: 0, 3: 0, 4: 0, 5: D, 6: nh, 7: S, 8: S, 9: D, 10: B, 11: 2 * D,
                                     **({12: kb} if beam else {})},
                                  f={0: 64 ** -0.5}))
@@ -454,19 +477,27 @@ class _DecodePlans(_StepPlans):
     depends on the row count (launch-bound GEMMs over 128 rows) — per micro-batch that was 29 ms, 80 ms of a 750 ms step.  Here the
     cross-attention K / V of every micro-batch are copied (6 x 460 MB per 128 crops, ~1 ms) into the row range of ONE decode plan over
     B rows, which then runs its 20 steps once.  Rows are independent: ids per crop are what the per-micro-batch decode produces
-    (same kernels; the split-K choice of the step GEMMs, hence the last bits of the logits, depends on the row count)."""
+    (same kernels; the split-K choice of the step GEMMs, hence the last bits of the logits, depends on the row count).
 
-    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, beam=None):
+    n_txt: text capacity of the micro-batches' plans when the prompt is an input (`_CaptionPlans`); `nkeys` is then the merged
+    table of valid encoder keys per crop, copied from the micro-batches like the K / V (`_encode_into`)."""
+
+    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, beam=None, n_txt=None):
         w, dev, dt = cap.w, cap.device, cap.dtype
         self.B, self.R = B, R
-        S = (R // 32) ** 2 + 1 + len(PROMPT_IDS)
+        S = (R // 32) ** 2 + 1 + (len(PROMPT_IDS) if n_txt is None else n_txt)
         self.S = S
+        self.n_txt = n_txt
         pk = PlanBuilder(dev, dt)
+        self.nkeys = None
+        if n_txt is not None:
+            self.nkeys = pk.raw((B,), torch.int32)
+            self.nkeys.fill_(S)        # rows behind the last crop are decoded too: all (zero) keys, as without a table
         # zero-initialised: the rows behind the last crop are never written (the micro-batches copy their own rows only) but ARE decoded;
         # recycled allocator memory there can hold NaN bit patterns, whose logits are all-NaN rows (found by the one-process GPU suite)
         self.cross_kv = [pk.alloc(B, S, 1, 2 * w.d_model, zero=True) for _ in range(w.dec_layers)]
         self._keep = pk.keep
-        self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam)
+        self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam, nkeys=self.nkeys)
         self.free_evt = None       # recorded behind the decode that last used this plan on another stream (pipelined batches)
         self._warm_up_and_capture(cap, self.step_plan)
 
@@ -477,11 +508,21 @@ class _CaptionPlans(_StepPlans):
     arena: another _CaptionPlans of the same resolution and a capacity >= B whose BUFFERS this one uses (round 6).  Such a plan set is
     encode-only: the same op list over the first B rows of every tensor of `arena` (PlanBuilder._from_arena), captured as its own
     hipGraph — the last micro-batch of a caption batch then computes exactly its own rows instead of a padded bucket (89 rows instead
-    of 96 at the benched load), without a second set of activations (~19 GB at 96 rows).  Built on demand by `encode_rows`."""
+    of 96 at the benched load), without a second set of activations (~19 GB at 96 rows).  Built on demand by `encode_rows`.
+
+    n_txt = None: the default prompt, a constant block of len(PROMPT_IDS) embedding rows baked into the plan (no table, no mask:
+    op for op what it always was).  n_txt in TEXT_CAPACITIES: the prompt is a plan INPUT like the pixels — `prompt_ids`
+    i32 [B, n_txt] (right-padded with the pad token) and `nkeys` i32 [B] = n_img + prompt length, written by `set_prompt` on the
+    plan's stream before a replay.  OMNI_OP_ASSEMBLE gathers the embedding rows on the device, the encoder self-attention and the
+    decoder cross-attention give keys at or beyond nkeys[b] no weight.  Padded positions are computed as queries (they hold the
+    pad token's embedding, attend to the valid keys, stay finite) and are read by nobody."""
 
     def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None,
-                 beam=None):
+                 beam=None, n_txt=None):
         w, dev, dt = cap.w, cap.device, cap.dtype
+        if arena is not None:
+            n_txt = arena.n_txt
+        self.n_txt = n_txt
         sd = w.sd
         self.B, self.R, self.T = B, R, max_new + 1
         pb = PlanBuilder(dev, dt)
@@ -674,13 +715,26 @@ class _CaptionPlans(_StepPlans):
         self.img_feat = img_feat
         # ---------------- encoder
         lm = "model.language_model."
-        S = n_img + len(PROMPT_IDS)
+        S = n_img + (len(PROMPT_IDS) if n_txt is None else n_txt)
         self.S = S
-        txt = W.cached(("prompt", dt), lambda: pb.upload((sd[lm + "shared.weight"][torch.tensor(PROMPT_IDS)] * w.embed_scale).to(torch_dtype(dt))))
-        pb.keep.append(txt)
-        enc = pb.alloc(B, S, 1, D)
-        pb.add_op(L.make_op(L.OP_ASSEMBLE, dt, p=[img_feat.ptr, txt.data_ptr(), None, None, enc.ptr],
-                            i={0: B, 1: n_img, 2: len(PROMPT_IDS), 3: D}))
+        self.prompt_ids = self.nkeys = None
+        if n_txt is None:
+            txt = W.cached(("prompt", dt), lambda: pb.upload((sd[lm + "shared.weight"][torch.tensor(PROMPT_IDS)] * w.embed_scale).to(torch_dtype(dt))))
+            pb.keep.append(txt)
+            enc = pb.alloc(B, S, 1, D)
+            pb.add_op(L.make_op(L.OP_ASSEMBLE, dt, p=[img_feat.ptr, txt.data_ptr(), None, None, enc.ptr],
+                                i={0: B, 1: n_img, 2: len(PROMPT_IDS), 3: D}))
+        else:
+            table, _ = W.token_tables()
+            pb.keep.append(table)
+            self.prompt_ids = pb.raw((B, n_txt), torch.int32)
+            self.nkeys = pb.raw((B,), torch.int32)
+            if arena is None:                      # (a twin shares the arena's two tensors: rows beyond a batch keep valid content)
+                self.prompt_ids.fill_(w.pad)
+                self.nkeys.fill_(S)
+            enc = pb.alloc(B, S, 1, D)
+            pb.add_op(L.make_op(L.OP_ASSEMBLE, dt, p=[img_feat.ptr, None, self.prompt_ids.data_ptr(), table.data_ptr(), enc.ptr],
+                                i={0: B, 1: n_img, 2: n_txt, 3: D, 4: table.shape[0]}, f={0: w.embed_scale}))
         encpos = W.cached(("encpos", S, dt), lambda: pb.upload(sd[lm + "encoder.embed_positions.weight"][2:2 + S].to(torch_dtype(dt))))
         pb.keep.append(encpos)
         xa = pb.alloc(B, S, 1, D)
@@ -696,7 +750,8 @@ class _CaptionPlans(_StepPlans):
         for l in range(w.enc_layers):
             pre = f"{lm}encoder.layers.{l}."
             linear(None, xin, qkv, keys=[pre + "self_attn.q_proj", pre + "self_attn.k_proj", pre + "self_attn.v_proj"])
-            pb.add_op(L.make_op(L.OP_ATTN_ROWS, dt, p=[qkv.ptr, qkv.ptr, qkv.ptr, None, att.ptr],
+            pb.add_op(L.make_op(L.OP_ATTN_ROWS, dt, p=[qkv.ptr, qkv.ptr, qkv.ptr, None, att.ptr]
+                                + ([None, None, self.nkeys.data_ptr()] if self.nkeys is not None else []),
                                 i={0: 3 * D, 1: 3 * D, 2: 3 * D, 3: D, 4: 0, 5: D, 6: 2 * D, 7: 0, 8: nh, 9: S, 10: S, 11: B,
                                    12: 0, 15: 64, 16: 1 if (attn_split and dma_enc) else 0}, f={0: 64 ** -0.5}))
             att.fmt = "split" if (attn_split and dma_enc) else "f32"
@@ -727,8 +782,15 @@ class _CaptionPlans(_StepPlans):
                 self.encode_plan.capture(stream or cap.stream)
             return
         # ---------------- decoder step plan (for a single micro-batch; batches of several micro-batches decode through _DecodePlans)
-        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam)
+        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys)
         self._warm_up_and_capture(cap, self.encode_plan, self.step_plan)
+
+    def set_prompt(self, ids: torch.Tensor, nkeys: torch.Tensor, n: int):
+        """write the prompt of rows [0, n) — ids i32 [n, n_txt] (or [1, n_txt] for all rows), nkeys i32 [n] (or [1]) — on the
+        current stream, before the encode plan is replayed (a twin of `encode_rows` reads the same two tensors)"""
+        assert self.prompt_ids is not None and ids.shape[-1] == self.n_txt and n <= self.B
+        self.prompt_ids[:n].copy_(ids.expand(n, -1), non_blocking=True)
+        self.nkeys[:n].copy_(nkeys.expand(n), non_blocking=True)
 
     def rows_for(self, cap: "Florence2Captioner", n: int) -> int:
         """Row count of the graph a micro-batch of n < B crops runs in this plan set's buffers.  Building a twin costs what building a
@@ -914,29 +976,89 @@ class Florence2Captioner:
         return (k, lp, es)
 
     @torch.inference_mode()
-    def decode_plans(self, B, R, max_new, slot=0, beam=None) -> _DecodePlans:
+    def decode_plans(self, B, R, max_new, slot=0, beam=None, n_txt=None) -> _DecodePlans:
         """slot: the pipelined stream (pipeline.py::parse_stream) decodes batch i on its own HIP stream while batch i+1 encodes, so it
         alternates between two decode plans (8 GB of cross-attention K/V each at 384 rows, 768x768 crops).  beam: see
-        `beam_config` (B crops = B k decoder rows)."""
+        `beam_config` (B crops = B k decoder rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`)."""
         key = ("dec", B, R, max_new) if slot == 0 else ("dec", B, R, max_new, slot)
-        if beam:
-            key = ("dec", B, R, max_new, slot, beam)
-        return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam))
+        if beam or n_txt is not None:
+            key = ("dec", B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
+        return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam, n_txt=n_txt))
 
     @torch.inference_mode()
-    def plans(self, B, R, max_new, slot=0, beam=None) -> _CaptionPlans:
+    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None) -> _CaptionPlans:
         """slot 1 = a second, independent set of buffers of the same capacity: the pipelined stream (pipeline.py::parse_stream) keeps two
         128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without).
-        beam: see `beam_config` (the step plan decodes B k rows)."""
+        beam: see `beam_config` (the step plan decodes B k rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`);
+        it is part of the cache key, None = the default prompt's plan."""
         key = (B, R, max_new) if slot == 0 else (B, R, max_new, slot)
-        if beam:
-            key = (B, R, max_new, slot, beam)
-        return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam))
+        if beam or n_txt is not None:
+            key = (B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
+        return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam, n_txt=n_txt))
+
+    # ---- prompts
+    def prompt_batch(self, rows, R):
+        """The caller's prompts as plan inputs.  rows: one list of token ids per image (bos ... eos, no padding).  Returns None when
+        every row is the default prompt PROMPT_IDS — such a batch runs the plan it always ran, at no cost — else
+        (ids i32 [n, n_txt] right-padded with the pad token, valid encoder keys i32 [n] = n_img + length, n_txt) on the host, n_txt
+        the smallest of TEXT_CAPACITIES that holds the longest row.  ValueError: an empty prompt, more than 64 tokens (plans at
+        768x768 are several GB each, so the capacity ladder stops there), an id outside the token table (refused here: the kernel
+        must not be the one to find out)."""
+        rows = [[int(t) for t in r] for r in rows]
+        if all(r == PROMPT_IDS for r in rows):
+            return None
+        vocab = self.w.sd["model.language_model.shared.weight"].shape[0]
+        for r in rows:
+            if not r:
+                raise ValueError("an empty prompt: at least one token is needed")
+            bad = [t for t in r if not 0 <= t < vocab]
+            if bad:
+                raise ValueError(f"prompt token id {bad[0]} is outside the token table (0..{vocab - 1})")
+        n_txt = text_capacity(max(len(r) for r in rows))
+        n_img = (R // 32) ** 2 + 1
+        ids = torch.full((len(rows), n_txt), int(self.w.pad), dtype=torch.int32)
+        for b, r in enumerate(rows):
+            ids[b, :len(r)] = torch.tensor(r, dtype=torch.int32)
+        nkeys = torch.tensor([n_img + len(r) for r in rows], dtype=torch.int32)
+        return ids, nkeys, n_txt
+
+    def _prompt_from_input_ids(self, input_ids, attention_mask, n, R):
+        """`prompt_batch` of generate()'s input_ids [n, n_img + L] (+ attention_mask of the same shape)"""
+        if input_ids is None:
+            if attention_mask is not None:
+                raise ValueError("attention_mask without input_ids")
+            return None
+        ids = torch.as_tensor(input_ids).detach().cpu().long()
+        n_img = (R // 32) ** 2 + 1
+        img_tok = int(self.w.cfg.get("image_token_id", 51289))
+        if ids.dim() != 2 or ids.shape[0] != n:
+            raise ValueError(f"input_ids must be [batch, tokens] with one row per image ({n}), got {tuple(ids.shape)}")
+        if ids.shape[1] <= n_img or not bool((ids[:, :n_img] == img_tok).all()):
+            raise ValueError(f"input_ids must start with the {n_img} image placeholder tokens (id {img_tok}) of a {R}x{R} image, "
+                             "followed by the prompt")
+        txt = ids[:, n_img:]
+        if attention_mask is None:
+            lens = [txt.shape[1]] * n
+        else:
+            m = torch.as_tensor(attention_mask).detach().cpu()
+            if tuple(m.shape) != tuple(ids.shape):
+                raise ValueError(f"attention_mask {tuple(m.shape)} does not match input_ids {tuple(ids.shape)}")
+            m = m != 0
+            if not bool(m[:, :n_img].all()):
+                raise ValueError("attention_mask hides image tokens: only prompt padding can be masked")
+            mt = m[:, n_img:]
+            lens = mt.sum(1).tolist()
+            if not bool((mt == (torch.arange(txt.shape[1])[None, :] < mt.sum(1)[:, None])).all()):
+                raise ValueError("attention_mask must be right-padded (ones, then zeros): left padding and holes are not supported")
+        return self.prompt_batch([txt[b, :lens[b]].tolist() for b in range(n)], R)
 
     # ---- merged decode (several micro-batches): encode only, cross-KV into rows [row0, row0 + n) of the decode plan
     def _encode_into(self, cp: _CaptionPlans, n: int, dec: _DecodePlans, row0: int, stream=None):
         """encode on `stream` (default: the captioner's first stream; the caller made it current)."""
         stream = stream or self.stream
+        assert cp.n_txt == dec.n_txt, "the micro-batches and their merged decode plan have one text capacity"
+        if dec.nkeys is not None:
+            dec.nkeys[row0:row0 + n].copy_(cp.nkeys[:n], non_blocking=True)
         if n < cp.B and self.exact_rows:
             cp = cp.encode_rows(self, cp.rows_for(self, n), stream)     # n rows (or the ladder capacity above n) in cp's buffers; cross_kv
                                                                         # below: the first n rows of the same tensors
@@ -1022,15 +1144,22 @@ class Florence2Captioner:
 
     @torch.inference_mode()
     def generate(self, input_ids=None, pixel_values=None, max_new_tokens=20, num_beams=1, do_sample=False, num_return_sequences=1,
-                 length_penalty=None, early_stopping=None, return_dict_in_generate=False, **kw):
+                 length_penalty=None, early_stopping=None, return_dict_in_generate=False, attention_mask=None, **kw):
         """hf-compatible entry point (ref:util/utils.py:125).  pixel_values: [B,3,R,R] float (NCHW).
+
+        input_ids [B, n_img + L]: the first n_img = (R / 32)^2 + 1 columns must be the image placeholder token (anything else is a
+        ValueError, not a guess), the rest is the prompt, right-padded when rows differ in length, with an attention_mask of the
+        same shape that is 1 on the image columns and on each row's prompt (left padding is a ValueError).  WITHOUT attention_mask
+        EVERY column counts — transformers would infer a mask from pad ids when pad != eos; here a pad id without a mask is a
+        prompt token.  Up to 64 prompt tokens (`text_capacity`).  input_ids=None, or rows that all equal PROMPT_IDS: the default
+        <CAPTION> prompt, on the plan it always ran on.  Works with num_beams > 1 as well.
 
         num_beams = 1: greedy decoding (the reference's call).  num_beams = 2..8: beam search on the device, transformers'
         `_beam_search` step for step (OMNI_OP_BEAM_STEP); `num_return_sequences` best hypotheses per image (image-major rows),
         `length_penalty` / `early_stopping` default to the checkpoint's generation settings.  return_dict_in_generate=True returns
         an object with `.sequences` and `.sequences_scores` (hf's beam scores; None for greedy decoding).  The default stays
         num_beams=1 although transformers would take num_beams=3 from Florence-2's generation config: changing it would change what
-        existing callers get.  Sampling is not implemented; the caller's input_ids are not read (fixed <CAPTION> prompt)."""
+        existing callers get.  Sampling is not implemented."""
         if do_sample:
             raise NotImplementedError("sampling is not implemented (greedy or beam search decoding)")
         beam = self.beam_config(num_beams, length_penalty, early_stopping)
@@ -1040,26 +1169,30 @@ class Florence2Captioner:
         with self._lock:
             Bn, _, R, R2 = pixel_values.shape
             assert R == R2
+            prompt = self._prompt_from_input_ids(input_ids, attention_mask, Bn, R)
 
             def fill(cp, s, n):
                 cp.x_in.t[:n, :, :, :3] = pixel_values[s:s + n].to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
-            seq, scores = self._results(self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill), beam,
+            seq, scores = self._results(self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill, prompt), beam,
                                         num_return_sequences)
         return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
 
-    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill):
+    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None):
         """encode + decode n_all images in chunks of `chunk` on the captioner's stream, each on the plan of its bucket: fill(cp, s, n)
-        writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  The `_run` result of
-        every chunk, for `_results`."""
+        writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  prompt: `prompt_batch`
+        of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results`."""
+        n_txt = prompt[2] if prompt else None
         if src.is_cuda:                                     # pixels / a screenshot the caller is still producing on its own stream
             self.stream.wait_stream(torch.cuda.current_stream(src.device))
         parts = []
         for s in range(0, n_all, chunk):
             n = min(chunk, n_all - s)
-            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam)
+            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam, n_txt=n_txt)
             with torch.cuda.stream(self.stream):
                 cp.reset()
                 fill(cp, s, n)
+                if prompt:
+                    cp.set_prompt(prompt[0][s:s + n].to(self.device, non_blocking=True), prompt[1][s:s + n].to(self.device, non_blocking=True), n)
                 parts.append(self._run(cp, n, max_new_tokens))
         return parts
 
@@ -1082,19 +1215,22 @@ class Florence2Captioner:
         return ids[:, :T].contiguous(), scores
 
     @torch.inference_mode()
-    def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None):
+    def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None,
+                      prompt_ids=None):
         """Fused fast path: crops are cut, resized (cv2-bilinear 64x64, then Pillow-bicubic to R on the
         768 path) and normalised on device from the HBM-resident screenshot (ref:util/utils.py:97-123).
         num_beams: None = `self.num_beams` (default 1, greedy); k > 1 = beam search, the best hypothesis per crop (what
-        generate(num_beams=k) returns for the same pixels)."""
+        generate(num_beams=k) returns for the same pixels).
+        prompt_ids: one list of token ids (bos ... eos) for all crops, None = the default PROMPT_IDS; see `prompt_batch`."""
         beam = self.beam_config(num_beams)
+        prompt = self.prompt_batch([list(prompt_ids)] * len(boxes_px), self.resolution) if prompt_ids is not None and len(boxes_px) else None
         batch_size = max(1, min(int(batch_size), 128))      # plan capacity: buckets stop at 128 crops (the reference's default batch)
 
         def fill(cp, s, n):
             rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
             self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
         with self._lock:
-            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill)
+            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt)
         if not parts:
             return torch.zeros((0, 1), dtype=torch.long)
         return self._results(parts, beam)[0]

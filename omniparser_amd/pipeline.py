@@ -278,20 +278,44 @@ class ScreenParser:
 
     # ---- stage 3: caption all crops of all frames in packed micro-batches
     @torch.inference_mode()
-    def caption(self, frames: Sequence[torch.Tensor], crops_per_frame, max_new_tokens=None, crops_dev: Optional[torch.Tensor] = None):
+    def caption(self, frames: Sequence[torch.Tensor], crops_per_frame, max_new_tokens=None, crops_dev: Optional[torch.Tensor] = None,
+                prompt=None):
         """crops_per_frame: host rectangles per frame, or — with `crops_dev` (int32 [frames, max_det, 4] on the device, rows in
-        caption order) — just the number of crops per frame: the rectangles then never visit the host."""
-        return self.caption_finish(self.caption_launch(frames, crops_per_frame, max_new_tokens, crops_dev))
+        caption order) — just the number of crops per frame: the rectangles then never visit the host.  prompt: see `prompt_ids`."""
+        return self.caption_finish(self.caption_launch(frames, crops_per_frame, max_new_tokens, crops_dev, prompt=prompt))
+
+    def prompt_ids(self, prompt):
+        """one caption prompt for a call: None (the default <CAPTION> prompt), text (a Florence-2 task token or free text, tokenised
+        by the parser's processor) or a list of token ids (bos ... eos) -> list of ids, or None"""
+        if prompt is None:
+            return None
+        if isinstance(prompt, str):
+            return self.proc.prompt_ids(prompt)
+        return [int(t) for t in prompt]
 
     @torch.inference_mode()
     def caption_launch(self, frames: Sequence[torch.Tensor], crops_per_frame, max_new_tokens=None, crops_dev: Optional[torch.Tensor] = None,
-                       overlap=False):
+                       overlap=False, prompt=None):
         """queue the crop / encode / decode work of every micro-batch on the captioner's stream; nothing is read back.  The handle
         keeps the frames alive until `caption_finish`.  overlap (parse_stream): micro-batches alternate between `self.encode_lanes`
         HIP streams, and the merged decode runs on a further stream on one of two alternating decode plans, so the next batch's
-        encode does not wait for it."""
+        encode does not wait for it.  prompt: one prompt for every crop of the call (`prompt_ids`); the default prompt takes the
+        plans it always took."""
         cap = self.cap
         R = cap.resolution
+        prompt = self.prompt_ids(prompt)
+        pr = cap.prompt_batch([prompt], R) if prompt is not None else None      # (ids [1, n_txt], keys [1], n_txt) or None = default
+        pkw = {}
+        if pr is not None:
+            pkw = {"n_txt": pr[2]}
+            # the device copies are read by copies queued on the lane streams: they stay alive in a small cache (a stream uses one prompt)
+            held = self.__dict__.setdefault("_prompt_dev", {})
+            if (tuple(prompt), R) not in held:
+                if len(held) >= 8:
+                    torch.cuda.synchronize(cap.device)
+                    held.clear()
+                held[(tuple(prompt), R)] = (pr[0].to(cap.device), pr[1].to(cap.device))
+            pr_ids, pr_keys = held[(tuple(prompt), R)]
         max_new_tokens = max_new_tokens or self.max_new_tokens
         if crops_dev is not None:
             flat = [(fi, k) for fi, n in enumerate(crops_per_frame) for k in range(int(n))]
@@ -309,7 +333,7 @@ class ScreenParser:
         if overlap and merged:
             self._dec_slot = 1 - getattr(self, "_dec_slot", 1)
         bkw = {"beam": beam} if beam else {}
-        dec = cap.decode_plans(cap.decode_bucket(len(flat)), R, max_new_tokens, slot=self._dec_slot if overlap else 0, **bkw) if merged else None
+        dec = cap.decode_plans(cap.decode_bucket(len(flat)), R, max_new_tokens, slot=self._dec_slot if overlap else 0, **bkw, **pkw) if merged else None
         if merged and not overlap:
             with torch.cuda.stream(cap.stream):
                 dec.reset()
@@ -327,9 +351,9 @@ class ScreenParser:
             # the buffers of ITS LANE's full-capacity plan set (florence.py::_CaptionPlans.encode_rows, taken inside `_encode_into`);
             # otherwise (single micro-batch, OMNI_EXACT_ROWS=0) a padded bucket plan with buffers of its own
             if merged and cap.exact_rows and n < self.batch_size:
-                cp = cap.plans(cap.bucket(self.batch_size), R, max_new_tokens, slot=lane)
+                cp = cap.plans(cap.bucket(self.batch_size), R, max_new_tokens, slot=lane, **pkw)
             else:
-                cp = cap.plans(cap.bucket(n), R, max_new_tokens, slot=lane if n == self.batch_size else 0, **({} if merged else bkw))
+                cp = cap.plans(cap.bucket(n), R, max_new_tokens, slot=lane if n == self.batch_size else 0, **({} if merged else bkw), **pkw)
             with torch.cuda.stream(stream):
                 if cp.free_evt is not None:
                     stream.wait_event(cp.free_evt)
@@ -349,6 +373,8 @@ class ScreenParser:
                     rects = crops_dev[fi, chunk[o][1]:] if crops_dev is not None else bx[o:]     # rows of one frame are contiguous
                     cap.launch_crops(cp, o, e - o, frames[fi], rects, c64[o:], tmp[o:] if tmp is not None else None, stream)
                     o = e
+                if pr is not None:
+                    cp.set_prompt(pr_ids, pr_keys, n)
                 if merged:
                     cap._encode_into(cp, n, dec, s, stream)
                 else:
@@ -427,22 +453,26 @@ class ScreenParser:
 
     @torch.inference_mode()
     def parse_batch(self, frames: Sequence[torch.Tensor], ocr: Optional[Sequence] = None, return_ids=False,
-                    pad_to: Optional[int] = None):
+                    pad_to: Optional[int] = None, prompt=None):
         """frames: uint8 [H,W,3] device tensors (same size); ocr: per frame (texts, xyxy px boxes) or None;
-        pad_to: detector plan batch size to use when fewer frames arrive (see `detect`)."""
+        pad_to: detector plan batch size to use when fewer frames arrive (see `detect`); prompt: the caption prompt of this call
+        (`prompt_ids`: text or token ids; None = <CAPTION>)."""
         ih, iw = frames[0].shape[:2]
+        prompt = self.prompt_ids(prompt)
         with self.det._lock, self.cap._lock:
-            return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to)
+            return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to, prompt)
 
-    def parse_stream(self, batches, return_ids=False, pad_to: Optional[int] = None):
+    def parse_stream(self, batches, return_ids=False, pad_to: Optional[int] = None, prompt=None):
         """Generator over an iterable of (frames, ocr) batches -> what `parse_batch` returns for each, in order, as a software
         pipeline: the detector pass and the host hand-off of batch i+1 run on a helper thread (their stream is the detector's)
         while the captions of batch i occupy the GPU, and the caption work of batch i+1 is queued BEFORE the read-back of batch i
         blocks — the GPU never waits for the host between batches.  Same kernels, same order per batch, same results as
-        `parse_batch`.  (Host hand-off only: with OMNI_DEVICE_GLUE the crop table of a batch lives in per-plan device buffers.)"""
+        `parse_batch`.  (Host hand-off only: with OMNI_DEVICE_GLUE the crop table of a batch lives in per-plan device buffers.)
+        prompt: one caption prompt for the whole stream (`prompt_ids`)."""
         from concurrent.futures import ThreadPoolExecutor
+        prompt = self.prompt_ids(prompt)
         if self.device_glue:
-            yield from self._parse_stream_device(batches, return_ids, pad_to)
+            yield from self._parse_stream_device(batches, return_ids, pad_to, prompt)
             return
 
         def stage_a(frames, ocr):
@@ -477,13 +507,13 @@ class ScreenParser:
                 nxt = next(it, None)
                 fut = helper.submit(stage_a, *nxt) if nxt is not None else None
                 with torch.inference_mode(), self.cap._lock:
-                    handle = self.caption_launch(frames, crops_all)
+                    handle = self.caption_launch(frames, crops_all, **({} if prompt is None else {"prompt": prompt}))
                 if pending is not None:
                     yield finish(pending)
                 pending = (handle, elems_all, crops_all, nbox)
             yield finish(pending)
 
-    def _parse_stream_device(self, batches, return_ids, pad_to):
+    def _parse_stream_device(self, batches, return_ids, pad_to, prompt=None):
         """parse_stream with the device hand-off (the default): four HIP streams, one host thread.  Batch i+1's detector + hand-off
         graph runs on the detector's stream while batch i encodes; its tables are snapshotted (`detect_glue`) so nothing of batch i
         reads the detector plan's buffers afterwards; caption micro-batches alternate between two encode streams (the HBM-bound
@@ -500,11 +530,11 @@ class ScreenParser:
             return (elems_all, ids_out) if return_ids else elems_all
 
         try:
-            yield from self._stream_loop(batches, return_ids, pad_to, finish)
+            yield from self._stream_loop(batches, return_ids, pad_to, finish, prompt)
         finally:
             torch.cuda.synchronize(self.cap.device)      # an abandoned generator leaves no work behind on the side streams
 
-    def _stream_loop(self, batches, return_ids, pad_to, finish):
+    def _stream_loop(self, batches, return_ids, pad_to, finish, prompt=None):
         pending = None
         for frames, ocr in batches:
             ih, iw = frames[0].shape[:2]
@@ -515,12 +545,12 @@ class ScreenParser:
                 if pending is not None:
                     yield finish(pending)
                     pending = None
-                yield self.parse_batch(frames, ocr, return_ids=return_ids, pad_to=pad_to)
+                yield self.parse_batch(frames, ocr, return_ids=return_ids, pad_to=pad_to, **({} if prompt is None else {"prompt": prompt}))
                 continue
             snap, _, ocr_els, counts = handed
             n_crops = [int(counts[f, 1]) for f in range(len(frames))]
             with torch.inference_mode(), self.cap._lock:
-                handle = self.caption_launch(frames, n_crops, crops_dev=snap.crops, overlap=True)
+                handle = self.caption_launch(frames, n_crops, crops_dev=snap.crops, overlap=True, **({} if prompt is None else {"prompt": prompt}))
             if pending is not None:
                 yield finish(pending)
             pending = (handle, snap, ocr_els, counts, iw, ih, len(frames), n_crops)
@@ -554,14 +584,15 @@ class ScreenParser:
             ids_out.append([r for _, r in cl])
         return ids_out
 
-    def _parse_batch_locked(self, frames, ocr, return_ids, iw, ih, pad_to=None):
+    def _parse_batch_locked(self, frames, ocr, return_ids, iw, ih, pad_to=None, prompt=None):
         tiled = self.tile_large and (iw > 1952 or ih > 1112)
+        pkw = {} if prompt is None else {"prompt": prompt}       # no prompt: the calls they always were (subclasses override `caption`)
         handed = self.detect_glue(frames, ocr, pad_to) if (self.device_glue and not tiled) else None
         if handed is not None:
             dp, gs, ocr_els, counts = handed
             n_crops = [int(counts[f, 1]) for f in range(len(frames))]
             # crop rectangles were produced on the detector's stream, which the counts read-back above has drained: no event needed
-            caps = self.caption(frames, n_crops, crops_dev=gs.crops)
+            caps = self.caption(frames, n_crops, crops_dev=gs.crops, **pkw)
             elems_all = self.assemble(dp, gs, ocr_els, counts, iw, ih, len(frames))
             ids_out = self._fill_captions(elems_all, caps)
             self.stats = {"crops": n_crops, "boxes": [int(v) for v in dp.out_count[: len(frames)].tolist()], "stage_ms": self.stage_ms(),
@@ -577,7 +608,7 @@ class ScreenParser:
             texts, boxes = ocr[fi] if ocr is not None else ([], [])
             el, cr = self.glue(xy, iw, ih, boxes, texts)
             elems_all.append(el); crops_all.append(cr)
-        caps = self.caption(frames, crops_all)
+        caps = self.caption(frames, crops_all, **pkw)
         ids_out = self._fill_captions(elems_all, caps)
         self.stats = {"crops": [len(c) for c in crops_all], "boxes": [len(b) for b in det_boxes], "split_overflow": getattr(self, "range_overflow_last", 0)}
         self.last_crops = crops_all            # integer crop boxes per frame, in caption order (parity tests read them)

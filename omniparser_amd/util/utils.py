@@ -54,11 +54,29 @@ class _Batch(dict):
     __getattr__ = dict.get
 
 
+# Florence-2 task tokens that take no input -> the sentence the model was trained on (hf:models/florence2/processing_florence2.py,
+# `task_prompts_without_inputs`; restated, and compared with the installed transformers by the tests)
+TASK_PROMPTS = {
+    "<OCR>": "What is the text in the image?",
+    "<OCR_WITH_REGION>": "What is the text in the image, with regions?",
+    "<CAPTION>": "What does the image describe?",
+    "<DETAILED_CAPTION>": "Describe in detail what is shown in the image.",
+    "<MORE_DETAILED_CAPTION>": "Describe with a paragraph what is shown in the image.",
+    "<OD>": "Locate the objects with category name in the image.",
+    "<DENSE_REGION_CAPTION>": "Locate the objects in the image, with their descriptions.",
+    "<REGION_PROPOSAL>": "Locate the region proposals in the image.",
+}
+# task tokens whose sentence embeds an {input} (grounding / region tasks): refused — their answers are location tokens nobody here decodes
+TASKS_WITH_INPUT = ("<CAPTION_TO_PHRASE_GROUNDING>", "<REFERRING_EXPRESSION_SEGMENTATION>", "<REGION_TO_SEGMENTATION>",
+                    "<OPEN_VOCABULARY_DETECTION>", "<REGION_TO_CATEGORY>", "<REGION_TO_DESCRIPTION>", "<REGION_TO_OCR>")
+
+
 class FlorenceProcessor:
-    """Stand-in for AutoProcessor("microsoft/Florence-2-base") on the `<CAPTION>` path
+    """Stand-in for AutoProcessor("microsoft/Florence-2-base") on the caption path
     (hf:models/florence2/processing_florence2.py:84-152 + CLIP image processor).  Tokenizer files are
     not shipped with the reference; if `tokenizer.json` sits next to the checkpoint it is used for
-    `batch_decode`, otherwise token ids are rendered as text."""
+    `batch_decode` and for prompts other than `<CAPTION>`, otherwise token ids are rendered as text and only the
+    default prompt exists."""
 
     def __init__(self, model_dir=None, image_token_id=51289, special_ids=(0, 1, 2, 3)):
         """special_ids: bos / pad / eos / unk of the checkpoint (Florence2Captioner passes what generation_config.json says) — used
@@ -66,6 +84,9 @@ class FlorenceProcessor:
         `batch_decode(skip_special_tokens=True)` of the reference's AutoProcessor skips, ref:util/utils.py:128)."""
         self.image_token_id = image_token_id
         self.tok = None
+        self.model_dir = model_dir
+        sp = [int(i) for i in special_ids]
+        self.bos_id, self.pad_id, self.eos_id = sp[0], sp[1], sp[2]
         self.special = set(int(i) for i in special_ids) | {int(image_token_id)}
         if model_dir is not None and (Path(model_dir) / "tokenizer.json").exists():
             import json as _json
@@ -87,8 +108,39 @@ class FlorenceProcessor:
             arrs.append(torch.from_numpy(a.transpose(2, 0, 1).copy()))
         pix = torch.stack(arrs)
         n_img = (pix.shape[-1] // 32) ** 2 + 1
-        ids = torch.tensor([[self.image_token_id] * n_img + PROMPT_IDS] * len(imgs))
-        return _Batch(input_ids=ids, pixel_values=pix, attention_mask=torch.ones_like(ids))
+        if isinstance(text, (list, tuple)):
+            if len(text) != len(imgs):
+                raise ValueError(f"{len(text)} prompts for {len(imgs)} images")
+            rows = [self.prompt_ids(t) for t in text]
+        else:
+            rows = [self.prompt_ids(text)] * len(imgs)
+        T = max(len(r) for r in rows)                      # unequal prompts: right-padded, with the matching attention mask
+        ids = torch.tensor([[self.image_token_id] * n_img + r + [self.pad_id] * (T - len(r)) for r in rows])
+        mask = torch.tensor([[1] * (n_img + len(r)) + [0] * (T - len(r)) for r in rows])
+        return _Batch(input_ids=ids, pixel_values=pix, attention_mask=mask)
+
+    def prompt_ids(self, text=None):
+        """token ids (bos ... eos) of one prompt.  None and "<CAPTION>" are PROMPT_IDS, with or without a tokenizer.  The other
+        Florence-2 task tokens without an input stand for their task sentences (TASK_PROMPTS), any other string is tokenised as
+        it is: both need the `tokenizer.json` next to the checkpoint (ValueError naming the file when it is missing).  Task tokens
+        that need an {input} are a ValueError."""
+        if text is None or text == "<CAPTION>":
+            return list(PROMPT_IDS)
+        if not isinstance(text, str):
+            raise ValueError(f"a prompt is a string (got {type(text).__name__})")
+        for tk in TASKS_WITH_INPUT:
+            if tk in text:
+                raise ValueError(f"task {tk} needs an input and answers in location tokens: not supported by this captioner")
+        for tk, sentence in TASK_PROMPTS.items():
+            if tk in text:
+                if text != tk:
+                    raise ValueError(f"Task token {tk} should be the only content in the prompt.")
+                text = sentence
+                break
+        if self.tok is None:
+            where = Path(self.model_dir) / "tokenizer.json" if self.model_dir is not None else "tokenizer.json (no model directory was given)"
+            raise ValueError(f"the prompt {text!r} needs a tokenizer: {where} is missing (only the default <CAPTION> prompt works without it)")
+        return [self.bos_id] + list(self.tok.encode(text, add_special_tokens=False).ids) + [self.eos_id]
 
     def batch_decode(self, ids, skip_special_tokens=True):
         special = self.special
@@ -352,7 +404,9 @@ def crop_boxes_px(ratio_boxes, W, H):
 @torch.inference_mode()
 def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_model_processor, prompt=None, batch_size=128):
     """ref:util/utils.py:88-132.  Crops are cut/resized/normalised on device and captioned by the HIP
-    captioner; `image_source` may be the uint8 HWC numpy image (as in the reference) or a device tensor."""
+    captioner; `image_source` may be the uint8 HWC numpy image (as in the reference) or a device tensor.
+    prompt: the caption prompt of every crop, as the reference's (a Florence-2 task token or free text,
+    `FlorenceProcessor.prompt_ids`); None = `<CAPTION>`."""
     model, processor = caption_model_processor["model"], caption_model_processor["processor"]
     non_ocr = filtered_boxes[starting_idx:] if starting_idx else filtered_boxes
     H, W = image_source.shape[0], image_source.shape[1]
@@ -361,7 +415,9 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
         return []
     img_dev = image_source if isinstance(image_source, torch.Tensor) else torch.from_numpy(np.array(image_source, order="C"))   # writable copy (PIL views are read-only)
     img_dev = img_dev.to(model.device)
-    ids = model.caption_crops(img_dev, boxes_px, max_new_tokens=20, batch_size=batch_size)
+    # prompt=None / "<CAPTION>": the call it always was (captioners without the keyword keep working); else the processor's ids
+    pkw = {} if prompt is None or prompt == "<CAPTION>" else {"prompt_ids": processor.prompt_ids(prompt)}
+    ids = model.caption_crops(img_dev, boxes_px, max_new_tokens=20, batch_size=batch_size, **pkw)
     texts = processor.batch_decode(ids, skip_special_tokens=True)
     return [t.strip() for t in texts]
 
