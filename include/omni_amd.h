@@ -216,7 +216,13 @@ enum {
    * a primitive list, in order.  p0 frame u8[H,W,3] (in / out) p1 primitives i32[n,8] = {kind, x0, y0, x1, y1, r | g<<8 | b<<16,
    * a, 0}: kind 0 filled rectangle (x1, y1 inclusive), 1 ring = the pixels of the rectangle that are not in its interior shrunk by
    * a = width on every side, 2 coverage mask (x1, y1 exclusive; a = byte offset of its (y1-y0) x (x1-x0) u8 mask in p2) blended
-   * like Pillow's draw_bitmap; p2 masks u8.  i0 H i1 W i2 n */
+   * like Pillow's draw_bitmap; p2 masks u8.  i0 H i1 W i2 n
+   *  Frame batch (additive; p3 = p4 = NULL and i3 = 0: the in-place form above): ONE launch over i3 = B >= 1 equal-sized frames, OUT OF
+   *  PLACE — p0 destination u8[B,H,W,3], every pixel of it is written (the source value where nothing draws; a frame without
+   *  primitives is a copy); p3 device table of B source frame pointers (u8[H,W,3] each, never written, may not overlap p0);
+   *  p1 the primitive lists of all frames one after the other, i2 their total; p4 i32[B + 1] offsets: frame f draws primitives
+   *  p4[f] .. p4[f + 1]; p2 ONE mask blob, the `a` of a kind-2 primitive is its ABSOLUTE byte offset in it.  Either of p3 / p4 / i3
+   *  set selects this form, and then a NULL p3 / p4 or B < 1 is OMNI_E_ARG */
   OMNI_OP_OVERLAY = 21,
   /* Frame -> PNG file -> base64, all on the device (ref:util/utils.py:485-488: PIL save(format="PNG") + base64.b64encode):
    * signature, IHDR (8-bit RGB), ONE IDAT whose zlib stream holds stored deflate blocks (filter 0 scanlines; 65535-byte blocks),
@@ -238,7 +244,12 @@ enum {
    *  block per unit (length-limited canonical codes built on the device) + the empty stored block; ~1.1x (desktop screenshots) ...
    *  1.3x (noise-heavy frames) the bytes of Pillow's zlib level 6 (the fixed-Huffman variant: 2.7x).  Needs p3 >= ceil(H (3 W + 1) /
    *  32768) * 33792 bytes and p7 = token scratch u32[ceil(H (3 W + 1) / 32768) * 32768]; same capacities otherwise.  Bytes =
-   *  oracle/png_ref.py::deflate_png_lz. */
+   *  oracle/png_ref.py::deflate_png_lz.
+   *  i5 = 2 (additive): the i5 = 1 stream for i6 = B >= 1 equal-sized frames in the SAME nine launches (frame = a grid dimension;
+   *  the per-unit encoder is the same code, so every file is deflate_png_lz of its frame).  p0 u8[B,H,W,3]; p1..p7 hold B parts one
+   *  after the other, each of the per-frame capacity of the i5 = 1 form: p1 [B][i2] p2 [B][H (3 W + 1)] p3 [B][units * 33792]
+   *  p4 [B][i3] p5 [B][i4] p6 [B][4 ceil(i2 / 3)] or NULL p7 [B][units * 32768]; i2 / i3 / i4 stay PER-FRAME capacities with the
+   *  same lower bounds.  B < 1 is OMNI_E_ARG.  i6 is ignored unless i5 = 2; the fixed-Huffman variant has no batched form */
   OMNI_OP_PNG_DEFLATE = 23,
   /* FFN of a DaViT block as one kernel (hf:models/florence2/modeling_florence2.py Florence2VisionMLP inside the residual of
    * Florence2VisionSpatialBlock / ChannelBlock): y = residual + fc2(GELU(fc1(x))), hidden activations kept in registers

@@ -186,6 +186,19 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
     case OMNI_OP_ATTN_DECODE:                                // p7: position table [B, cap] (self) or valid keys per cache row (cross)
       ext[7] = i[7] > 0 ? (long long)((i[10] + (i[12] > 1 ? i[12] : 1) - 1) / (i[12] > 1 ? i[12] : 1)) * 4 : (long long)i[10] * i[8] * 4;
       break;
+    case OMNI_OP_OVERLAY:                                    // the frame-batched form: whole buffers (one frame: first byte, as before)
+      if (op->p[3] || op->p[4] || i[3]) {
+        const long long B = i[3] > 0 ? i[3] : 1;
+        ext[0] = B * i[0] * i[1] * 3; ext[1] = (long long)i[2] * 32; ext[3] = B * 8; ext[4] = (B + 1) * 4;
+      }
+      break;
+    case OMNI_OP_PNG_DEFLATE:                                // i5 = 2: [frames][per-frame capacity] everywhere
+      if (i[5] == 2 && i[6] > 0 && i[0] > 0 && i[1] > 0) {
+        const long long B = i[6], U = (long long)i[0] * (3LL * i[1] + 1), units = (U + 32767) / 32768;
+        ext[0] = B * i[0] * i[1] * 3; ext[1] = B * i[2]; ext[2] = B * U; ext[3] = B * units * 33792; ext[4] = B * i[3] * 4;
+        ext[5] = B * i[4] * 4; ext[6] = B * 4 * (((long long)i[2] + 2) / 3); ext[7] = B * units * 32768 * 4;
+      }
+      break;
     default: break;
   }
   for (int k = 0; k < 8; ++k) if (ext[k] < 1) ext[k] = 1;

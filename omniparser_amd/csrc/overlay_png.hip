@@ -10,6 +10,8 @@
 //                     STORED deflate blocks (filter byte 0 per scanline), IEND; Adler-32 and CRC-32 are computed on the device
 //                     (per-segment partials, combined by one thread with the GF(2) shift operator x^(8 len) mod P), then the whole
 //                     file is base64-encoded.  Five small launches on one stream; the host reads back ASCII.
+// OMNI_OP_OVERLAY and the LZ form of OMNI_OP_PNG_DEFLATE also take a batch of B equal-sized frames in the same number of launches
+// (frame = grid.z of the overlay, grid.y of the nine PNG kernels): B x 190 unit lanes in flight instead of 190 at 1080p.
 // The byte layout is restated on the CPU in oracle/png_ref.py (test oracle); any PNG reader is the second check.
 #include "omni_internal.h"
 
@@ -19,6 +21,8 @@ namespace {
 struct OvArgs {
   unsigned char* img; const int* prim; const unsigned char* masks;
   int H, W, n;
+  // frame-batched form (p3 / i3): img = destination u8[B,H,W,3], srcs = B source frames, offs = int32[B + 1] into prim
+  const unsigned char* const* srcs; const int* offs;
 };
 constexpr int PRIM_INTS = 8;     // {kind, x0, y0, x1, y1, r | g << 8 | b << 16, a, b}
 enum { PRIM_FILL = 0, PRIM_RING = 1, PRIM_MASK = 2 };
@@ -29,6 +33,9 @@ __device__ __forceinline__ unsigned blend8(unsigned m, unsigned in, unsigned ink
   return (t + (t >> 8)) >> 8;
 }
 
+// BATCHED: frame = blockIdx.z, OUT OF PLACE (source frame from the pointer table, every destination pixel written, the source never);
+// the frame's primitives are prim[offs[f] .. offs[f + 1]).  Otherwise the in-place single-frame raster.
+template <bool BATCHED>
 __global__ __launch_bounds__(256) void overlay_kernel(OvArgs a) {
   __shared__ int sp[256 * PRIM_INTS];
   __shared__ unsigned char hit[256];
@@ -37,9 +44,17 @@ __global__ __launch_bounds__(256) void overlay_kernel(OvArgs a) {
   const int x = bx0 + tx, y = by0 + ty;
   const bool live = x < a.W && y < a.H;
   unsigned r = 0, g = 0, b = 0;
-  unsigned char* px = a.img + ((long long)y * a.W + x) * 3;
-  if (live) { r = px[0]; g = px[1]; b = px[2]; }
-  bool dirty = false;
+  const long long pix = ((long long)y * a.W + x) * 3;
+  unsigned char* px = a.img + pix;
+  if (BATCHED) {
+    const int f = blockIdx.z;
+    px += (long long)f * a.H * a.W * 3;
+    const int o0 = a.offs[f];
+    a.prim += (long long)o0 * PRIM_INTS;
+    a.n = a.offs[f + 1] - o0;
+    if (live) { const unsigned char* sx = a.srcs[f] + pix; r = sx[0]; g = sx[1]; b = sx[2]; }
+  } else if (live) { r = px[0]; g = px[1]; b = px[2]; }
+  bool dirty = BATCHED;
   for (int base = 0; base < a.n; base += 256) {
     const int c = base + (int)threadIdx.x;
     unsigned char h = 0;
@@ -255,10 +270,23 @@ struct DefArgs {
   const unsigned char* img; unsigned char* png; unsigned char* filt; unsigned char* slots; unsigned* meta; unsigned* part; unsigned char* b64;
   int H, W, nunits;
   long long U;
+  // frame-batched form (i5 = 2): distance in elements between the frames' parts of each buffer; all 0 for one frame
+  long long s_img, s_png, s_filt, s_slots, s_b64, s_toks;
+  int s_meta, s_part;
 };
 
+// the arguments of frame blockIdx.y (grid.y = frames; one frame: the arguments as they are)
+__device__ __forceinline__ DefArgs def_frame(DefArgs a) {
+  const long long f = blockIdx.y;
+  a.img += f * a.s_img; a.png += f * a.s_png; a.filt += f * a.s_filt; a.slots += f * a.s_slots;
+  a.meta += f * a.s_meta; a.part += f * a.s_part;
+  if (a.b64) a.b64 += f * a.s_b64;
+  return a;
+}
+
 // filtered scanline stream: row 0 filter 0 (None), other rows filter 2 (Up).  One thread per 4 stream bytes.
-__global__ __launch_bounds__(256) void png_filter_kernel(DefArgs a) {
+__global__ __launch_bounds__(256) void png_filter_kernel(DefArgs a_) {
+  const DefArgs a = def_frame(a_);
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int RB = 3 * a.W + 1;
 #pragma unroll
@@ -313,7 +341,8 @@ struct BitWriter {
 
 // one thread per unit: greedy run matching (distance 1 = byte runs, distance 3 = pixel runs; matches may reach back across the unit
 // start — the decoder's window holds those bytes), fixed-Huffman block + empty stored block; stored block if that is not smaller.
-__global__ __launch_bounds__(64) void png_deflate_units_kernel(DefArgs a) {
+__global__ __launch_bounds__(64) void png_deflate_units_kernel(DefArgs a_) {
+  const DefArgs a = def_frame(a_);
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= a.nunits) return;
   const long long start = (long long)u * UNIT;
@@ -349,8 +378,9 @@ __global__ __launch_bounds__(64) void png_deflate_units_kernel(DefArgs a) {
 }
 
 // one thread: unit offsets (exclusive scan), stream / file sizes, constant header bytes
-__global__ void png_layout_kernel(DefArgs a) {
-  if (threadIdx.x || blockIdx.x) return;
+__global__ void png_layout_kernel(DefArgs a_) {
+  if (threadIdx.x || blockIdx.x) return;            // one block per frame (grid.y)
+  const DefArgs a = def_frame(a_);
   unsigned off = 0;
   for (int u = 0; u < a.nunits; ++u) {
     const unsigned sz = a.meta[M_SIZES + u];
@@ -380,7 +410,8 @@ __global__ void png_layout_kernel(DefArgs a) {
 }
 
 // one wave per unit: slot -> its place in the stream
-__global__ __launch_bounds__(64) void png_gather_kernel(DefArgs a) {
+__global__ __launch_bounds__(64) void png_gather_kernel(DefArgs a_) {
+  const DefArgs a = def_frame(a_);
   const int u = blockIdx.x;
   const unsigned sz = a.meta[M_SIZES + u], off = a.meta[M_SIZES + a.nunits + u];
   const unsigned char* src = a.slots + (long long)u * SLOT;
@@ -490,9 +521,11 @@ __device__ void lz_canonical_codes(const unsigned char* lens, int n, int max_bit
   for (int s = 0; s < n; ++s) { codes[s] = 0; if (lens[s]) codes[s] = (unsigned short)nxt[lens[s]]++; }
 }
 
-__global__ __launch_bounds__(64) void png_lz_units_kernel(DefArgs a, unsigned* __restrict__ toks_all) {
+__global__ __launch_bounds__(64) void png_lz_units_kernel(DefArgs a_, unsigned* __restrict__ toks_all) {
   __shared__ LzWork w;
   if (threadIdx.x != 0) return;                          // one lane per unit (see the header comment)
+  const DefArgs a = def_frame(a_);
+  toks_all += (long long)blockIdx.y * a.s_toks;
   const int u = blockIdx.x;
   const long long start = (long long)u * UNIT_LZ;
   const long long end = min(start + (long long)UNIT_LZ, a.U);
@@ -644,7 +677,8 @@ __global__ __launch_bounds__(64) void png_lz_units_kernel(DefArgs a, unsigned* _
 }
 
 // one wave per unit: LZ slot -> its place in the stream
-__global__ __launch_bounds__(64) void png_lz_gather_kernel(DefArgs a) {
+__global__ __launch_bounds__(64) void png_lz_gather_kernel(DefArgs a_) {
+  const DefArgs a = def_frame(a_);
   const int u = blockIdx.x;
   const unsigned sz = a.meta[M_SIZES + u], off = a.meta[M_SIZES + a.nunits + u];
   const unsigned char* src = a.slots + (long long)u * SLOT_LZ;
@@ -653,7 +687,8 @@ __global__ __launch_bounds__(64) void png_lz_gather_kernel(DefArgs a) {
 }
 
 // Adler-32 partials over the rows of the FILTERED stream (filter byte included), same form as png_adler_rows_kernel
-__global__ __launch_bounds__(64) void png_adler_filt_kernel(DefArgs a) {
+__global__ __launch_bounds__(64) void png_adler_filt_kernel(DefArgs a_) {
+  const DefArgs a = def_frame(a_);
   const int row = blockIdx.x, lane = threadIdx.x;
   const int RB = 3 * a.W + 1;
   const unsigned char* src = a.filt + (long long)row * RB;
@@ -669,8 +704,9 @@ __global__ __launch_bounds__(64) void png_adler_filt_kernel(DefArgs a) {
 }
 
 // the fold / CRC kernels of the stored variant, with the stream length read from the device
-__global__ void png_def_adler_fold_kernel(DefArgs a) {
-  if (threadIdx.x || blockIdx.x) return;
+__global__ void png_def_adler_fold_kernel(DefArgs a_) {
+  if (threadIdx.x || blockIdx.x) return;            // one block per frame (grid.y)
+  const DefArgs a = def_frame(a_);
   const unsigned RB = (unsigned)(3 * a.W + 1);
   unsigned long long A = 1, B = 0;
   for (int r = 0; r < a.H; ++r) {
@@ -680,7 +716,8 @@ __global__ void png_def_adler_fold_kernel(DefArgs a) {
   put_be32(a.png + PNG_HEAD + a.meta[M_Z] - 4, (unsigned)((B << 16) | A));
 }
 
-__global__ __launch_bounds__(256) void png_def_crc_seg_kernel(DefArgs a) {
+__global__ __launch_bounds__(256) void png_def_crc_seg_kernel(DefArgs a_) {
+  const DefArgs a = def_frame(a_);
   __shared__ unsigned tab[256];
   tab[threadIdx.x] = crc_entry(threadIdx.x);
   __syncthreads();
@@ -697,8 +734,9 @@ __global__ __launch_bounds__(256) void png_def_crc_seg_kernel(DefArgs a) {
   a.part[2 * a.H + s] = c;
 }
 
-__global__ void png_def_crc_fold_kernel(DefArgs a) {
-  if (threadIdx.x || blockIdx.x) return;
+__global__ void png_def_crc_fold_kernel(DefArgs a_) {
+  if (threadIdx.x || blockIdx.x) return;            // one block per frame (grid.y)
+  const DefArgs a = def_frame(a_);
   unsigned xp = 1u << 30, op = 1u << 31;
   for (unsigned n = 8u * CRC_SEG; n; n >>= 1) {
     if (n & 1u) op = gf2_mul(xp, op);
@@ -710,9 +748,11 @@ __global__ void png_def_crc_fold_kernel(DefArgs a) {
   put_be32(a.png + PNG_HEAD + a.meta[M_Z], c ^ 0xffffffffu);
 }
 
-__global__ __launch_bounds__(256) void base64_dyn_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
-                                                         const unsigned* __restrict__ meta) {
-  const long long n = meta[M_TOTAL];
+__global__ __launch_bounds__(256) void base64_dyn_kernel(DefArgs a_) {
+  const DefArgs a = def_frame(a_);
+  const unsigned char* __restrict__ src = a.png;
+  unsigned char* __restrict__ dst = a.b64;
+  const long long n = a.meta[M_TOTAL];
   const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long i = g * 3;
   if (i >= n) return;
@@ -735,9 +775,18 @@ int omni_launch_overlay(const omni_op_t* op, hipStream_t s) {
   OvArgs a{};
   a.img = (unsigned char*)op->p[0]; a.prim = (const int*)op->p[1]; a.masks = (const unsigned char*)op->p[2];
   a.H = op->i[0]; a.W = op->i[1]; a.n = op->i[2];
+  if (op->p[3] || op->p[4] || op->i[3]) {                 // frame-batched, out of place: one launch for i3 frames
+    a.srcs = (const unsigned char* const*)op->p[3]; a.offs = (const int*)op->p[4];
+    const int B = op->i[3];
+    OMNI_REQUIRE(a.img && a.srcs && a.offs && B >= 1 && B <= 65535 && a.H > 0 && a.W > 0 && a.n >= 0 && (a.n == 0 || (a.prim && a.masks)),
+                 "overlay: bad arguments of the batched form (destination, source table, offsets, 1 <= frames)");
+    hipLaunchKernelGGL(overlay_kernel<true>, dim3((a.W + 63) / 64, (a.H + 3) / 4, B), dim3(256), 0, s, a);
+    OMNI_HIP_CHECK(hipGetLastError());
+    return OMNI_OK;
+  }
   OMNI_REQUIRE(a.img && a.H > 0 && a.W > 0 && a.n >= 0 && (a.n == 0 || a.prim), "overlay: bad arguments");
   if (a.n == 0) return OMNI_OK;
-  hipLaunchKernelGGL(overlay_kernel, dim3((a.W + 63) / 64, (a.H + 3) / 4), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(overlay_kernel<false>, dim3((a.W + 63) / 64, (a.H + 3) / 4), dim3(256), 0, s, a);
   OMNI_HIP_CHECK(hipGetLastError());
   return OMNI_OK;
 }
@@ -781,9 +830,12 @@ int omni_launch_png_deflate(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE(a.img && a.png && a.filt && a.slots && a.meta && a.part && a.H > 0 && a.W > 0 && a.H <= 32768 && a.W <= 32768,
                "png_deflate: bad arguments");
   a.U = (long long)a.H * (3 * a.W + 1);
-  const bool lz = op->i[5] == 1;                          // LZ77 + dynamic Huffman over 32 KiB units (p7 = token scratch, u32[units * 32768])
+  const bool batched = op->i[5] == 2;                     // the LZ variant over i6 frames: every buffer [frames][per-frame capacity]
+  const bool lz = op->i[5] == 1 || batched;               // LZ77 + dynamic Huffman over 32 KiB units (p7 = token scratch, u32[units * 32768])
+  const int B = batched ? op->i[6] : 1;
+  OMNI_REQUIRE(B >= 1 && B <= 65535, "png_deflate: i5 = 2 needs 1 <= i6 frames, got %d", B);
   unsigned* toks = (unsigned*)op->p[7];
-  OMNI_REQUIRE(!lz || toks, "png_deflate: i5 = 1 needs the token scratch p7");
+  OMNI_REQUIRE(!lz || toks, "png_deflate: i5 = 1 / 2 needs the token scratch p7");
   a.nunits = lz ? (int)((a.U + UNIT_LZ - 1) / UNIT_LZ) : (int)((a.U + UNIT - 1) / UNIT);
   const long long zmax = 2 + a.U + 5ll * ((a.U + UNIT - 1) / UNIT) + 4;     // capacity contract of the fixed-Huffman variant (covers both)
   OMNI_REQUIRE(zmax < (1ll << 31), "png_deflate: image too large for one IDAT chunk");
@@ -791,22 +843,25 @@ int omni_launch_png_deflate(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE(op->i[2] >= zmax + 57, "png_deflate: output holds %d bytes, worst case is %lld", op->i[2], zmax + 57);
   OMNI_REQUIRE(op->i[3] >= M_SIZES + 2 * a.nunits, "png_deflate: meta holds %d words, needs %d", op->i[3], M_SIZES + 2 * a.nunits);
   OMNI_REQUIRE(op->i[4] >= 2 * a.H + nseg_max, "png_deflate: scratch holds %d words, needs %d", op->i[4], 2 * a.H + nseg_max);
-  const long long quads = (a.U + 3) / 4;
-  hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a);
-  if (lz) hipLaunchKernelGGL(png_lz_units_kernel, dim3(a.nunits), dim3(64), 0, s, a, toks);
-  else hipLaunchKernelGGL(png_deflate_units_kernel, dim3((a.nunits + 63) / 64), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(png_layout_kernel, dim3(1), dim3(64), 0, s, a);
-  if (lz) hipLaunchKernelGGL(png_lz_gather_kernel, dim3(a.nunits), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(png_gather_kernel, dim3(a.nunits), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(png_adler_filt_kernel, dim3(a.H), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(png_def_adler_fold_kernel, dim3(1), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(png_def_crc_seg_kernel, dim3((nseg_max + 255) / 256), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(png_def_crc_fold_kernel, dim3(1), dim3(64), 0, s, a);
-  if (a.b64) {
-    const long long groups = (zmax + 57 + 2) / 3;
-    hipLaunchKernelGGL(base64_dyn_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const unsigned char*)a.png, a.b64,
-                       (const unsigned*)a.meta);
+  long long b64_groups = (zmax + 57 + 2) / 3;
+  if (batched) {                                          // frame f: its part of every buffer lies f capacities behind frame 0's
+    a.s_img = (long long)a.H * a.W * 3; a.s_png = op->i[2]; a.s_filt = a.U; a.s_slots = (long long)a.nunits * SLOT_LZ;
+    a.s_toks = (long long)a.nunits * UNIT_LZ; a.s_meta = op->i[3]; a.s_part = op->i[4];
+    a.s_b64 = 4ll * (((long long)op->i[2] + 2) / 3);
   }
+  const unsigned F = (unsigned)B;
+  const long long quads = (a.U + 3) / 4;
+  hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((quads + 255) / 256), F), dim3(256), 0, s, a);
+  if (lz) hipLaunchKernelGGL(png_lz_units_kernel, dim3(a.nunits, F), dim3(64), 0, s, a, toks);
+  else hipLaunchKernelGGL(png_deflate_units_kernel, dim3((a.nunits + 63) / 64), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(png_layout_kernel, dim3(1, F), dim3(64), 0, s, a);
+  if (lz) hipLaunchKernelGGL(png_lz_gather_kernel, dim3(a.nunits, F), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(png_gather_kernel, dim3(a.nunits), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(png_adler_filt_kernel, dim3(a.H, F), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(png_def_adler_fold_kernel, dim3(1, F), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(png_def_crc_seg_kernel, dim3((nseg_max + 255) / 256, F), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(png_def_crc_fold_kernel, dim3(1, F), dim3(64), 0, s, a);
+  if (a.b64) hipLaunchKernelGGL(base64_dyn_kernel, dim3((unsigned)((b64_groups + 255) / 256), F), dim3(256), 0, s, a);
   OMNI_HIP_CHECK(hipGetLastError());
   return OMNI_OK;
 }

@@ -451,28 +451,120 @@ class ScreenParser:
                 k += 1
         return out
 
+    # ---- stage 4 (return_image=True): the tail of get_som_labeled_img for the whole batch.  The overlay depends on the boxes only, which
+    #      are final once the hand-off has run, so it is queued on a stream of its own BEFORE the caption work and read back after it.
+    def _annotate_scratch(self, B, H, W, device):
+        """`U.AnnotateScratch` per (B, H, W), two alternating sets (parse_stream queues batch i+1 before it reads batch i back, and
+        reads batch i back before it queues batch i+2), cached on the parser, least recently used shape evicted first
+        (OMNI_MAX_ANNOTATE_SCRATCH shapes stay, default 2; `release_annotate_scratch` drops them all)."""
+        cache = self.__dict__.setdefault("_ann_scratch", {})
+        key = (B, H, W)
+        if key in cache:
+            cache[key] = cache.pop(key)
+        else:
+            keep = max(1, int(os.environ.get("OMNI_MAX_ANNOTATE_SCRATCH", "2")))
+            while len(cache) >= keep:
+                self._ann_stream.synchronize()           # the evicted buffers may still be in use on the annotate stream
+                cache.pop(next(iter(cache)))
+            cache[key] = [0, [None, None]]
+        ent = cache[key]
+        ent[0] = 1 - ent[0]
+        if ent[1][ent[0]] is None:
+            with torch.cuda.device(device):
+                ent[1][ent[0]] = U.AnnotateScratch(B, H, W, device)
+        return ent[1][ent[0]]
+
+    def release_annotate_scratch(self):
+        """free the cached overlay / PNG scratch (about 60 MB per 1080p frame and set); call it where the plans are cleared"""
+        if self.__dict__.get("_ann_scratch"):
+            self._ann_stream.synchronize()
+            self._ann_scratch.clear()
+
+    def annotate_hbm_bytes(self):
+        return sum(sc.nbytes() for ent in self.__dict__.get("_ann_scratch", {}).values() for sc in ent[1] if sc is not None)
+
+    @torch.inference_mode()
+    def _annotate_launch(self, frames, elems_all, iw, ih, draw_bbox_config=None):
+        """elems_all: the element lists of the batch (geometry final, captions not needed).  Labels are the running indices of each
+        list, boxes its `bbox` ratios, style `draw_bbox_config` or util.omniparser.overlay_style((w, h)).  On the device (`U.
+        overlay_on_device`): ONE overlay launch + ONE deflate chain on the annotate stream, behind everything the caller's and the
+        detector's streams hold so far, out of place — the caption crops read the same frames.  -> handle for `_annotate_finish`."""
+        from .util.omniparser import overlay_style
+        cfg = dict(draw_bbox_config or overlay_style((iw, ih)))
+        boxes = [U._box_convert_xyxy_to_cxcywh(torch.tensor([e["bbox"] for e in el], dtype=torch.float32).reshape(-1, 4)) for el in elems_all]
+        phrases = [list(range(len(el))) for el in elems_all]
+        dev = frames[0].device
+        if os.environ.get("OMNI_SKIP_ANNOTATE", "0") == "1":
+            return ("skip", boxes, phrases, iw, ih)
+        if not U.overlay_on_device(dev):
+            return ("host", list(frames), boxes, phrases, cfg)
+        if self.__dict__.get("_ann_stream") is None:
+            with torch.cuda.device(dev):
+                self._ann_stream = torch.cuda.Stream(dev)
+        st = self._ann_stream
+        st.wait_stream(torch.cuda.current_stream(dev))       # frames the caller is still producing on its stream
+        if self.det is not None and getattr(self.det, "stream", None) is not None:
+            st.wait_stream(self.det.stream)
+        sc = self._annotate_scratch(len(frames), ih, iw, dev)
+        self._ev["ann0"] = st.record_event(torch.cuda.Event(enable_timing=True))
+        handle = U.annotate_encode_device_batch_launch(frames, boxes, phrases, stream=st, scratch=sc, **cfg)
+        self._ev["ann1"] = st.record_event(torch.cuda.Event(enable_timing=True))
+        return ("device", handle)
+
+    @torch.inference_mode()
+    def _annotate_finish(self, handle):
+        """-> [(som_image_base64, label_coordinates)] per frame (pixel xywh, what `get_som_labeled_img` returns first and second)"""
+        if handle[0] == "device":
+            return U.annotate_encode_device_batch_finish(handle[1])
+        if handle[0] == "skip":
+            _, boxes, phrases, iw, ih = handle
+            out = []
+            for b, ph in zip(boxes, phrases):
+                cx, cy, bw, bh = (b * torch.Tensor([iw, ih, iw, ih])).unbind(-1)
+                xywh = torch.stack((cx - 0.5 * bw, cy - 0.5 * bh, bw, bh), -1).numpy()
+                out.append(("", {f"{k}": v for k, v in zip(ph, xywh)}))
+            return out
+        _, frames, boxes, phrases, cfg = handle
+        out = []
+        for f, b, ph in zip(frames, boxes, phrases):
+            frame, coords = U.annotate(f.cpu().numpy(), b, None, ph, **cfg)
+            out.append((U.encode_png_b64(frame), coords))
+        return out
+
+    @staticmethod
+    def _with_images(result, return_ids, images):
+        return (*result, images) if return_ids else (result, images)
+
     @torch.inference_mode()
     def parse_batch(self, frames: Sequence[torch.Tensor], ocr: Optional[Sequence] = None, return_ids=False,
-                    pad_to: Optional[int] = None, prompt=None):
+                    pad_to: Optional[int] = None, prompt=None, return_image=False, draw_bbox_config=None):
         """frames: uint8 [H,W,3] device tensors (same size); ocr: per frame (texts, xyxy px boxes) or None;
         pad_to: detector plan batch size to use when fewer frames arrive (see `detect`); prompt: the caption prompt of this call
-        (`prompt_ids`: text or token ids; None = <CAPTION>)."""
+        (`prompt_ids`: text or token ids; None = <CAPTION>).
+        return_image: the result gains a LAST member, per frame (som_image_base64, label_coordinates) — the set-of-marks PNG and
+        the pixel xywh of every element, the first two members of `get_som_labeled_img`'s result; labels are the running indices of
+        the frame's element list, style = draw_bbox_config or util.omniparser.overlay_style((w, h)).  The frames are not drawn on.
+        OMNI_OVERLAY=host: Pillow per frame; OMNI_SKIP_ANNOTATE=1: "" for the image."""
         ih, iw = frames[0].shape[:2]
         prompt = self.prompt_ids(prompt)
         with self.det._lock, self.cap._lock:
+            if return_image:
+                return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to, prompt, True, draw_bbox_config)
             return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to, prompt)
 
-    def parse_stream(self, batches, return_ids=False, pad_to: Optional[int] = None, prompt=None):
+    def parse_stream(self, batches, return_ids=False, pad_to: Optional[int] = None, prompt=None, return_image=False, draw_bbox_config=None):
         """Generator over an iterable of (frames, ocr) batches -> what `parse_batch` returns for each, in order, as a software
         pipeline: the detector pass and the host hand-off of batch i+1 run on a helper thread (their stream is the detector's)
         while the captions of batch i occupy the GPU, and the caption work of batch i+1 is queued BEFORE the read-back of batch i
         blocks — the GPU never waits for the host between batches.  Same kernels, same order per batch, same results as
         `parse_batch`.  (Host hand-off only: with OMNI_DEVICE_GLUE the crop table of a batch lives in per-plan device buffers.)
-        prompt: one caption prompt for the whole stream (`prompt_ids`)."""
+        prompt: one caption prompt for the whole stream (`prompt_ids`).  return_image / draw_bbox_config: as `parse_batch`; the
+        overlay + PNG work of a batch is queued on the annotate stream before its caption work and read back with its ids."""
         from concurrent.futures import ThreadPoolExecutor
         prompt = self.prompt_ids(prompt)
+        img = (True, draw_bbox_config) if return_image else None
         if self.device_glue:
-            yield from self._parse_stream_device(batches, return_ids, pad_to, prompt)
+            yield from self._parse_stream_device(batches, return_ids, pad_to, prompt, *(() if img is None else (img,)))
             return
 
         def stage_a(frames, ocr):
@@ -487,13 +579,14 @@ class ScreenParser:
                 return frames, elems_all, crops_all, [len(b) for b in det_boxes]
 
         def finish(pending):
-            handle, elems_all, crops_all, nbox = pending
+            handle, elems_all, crops_all, nbox, ann = pending
             with torch.inference_mode(), self.cap._lock:
                 caps = self.caption_finish(handle)
             ids_out = self._fill_captions(elems_all, caps)
             self.stats = {"crops": [len(c) for c in crops_all], "boxes": nbox, "split_overflow": getattr(self, "range_overflow_last", 0)}
             self.last_crops = crops_all
-            return (elems_all, ids_out) if return_ids else elems_all
+            res = (elems_all, ids_out) if return_ids else elems_all
+            return res if ann is None else self._with_images(res, return_ids, self._annotate_finish(ann))
 
         it = iter(batches)
         first = next(it, None)
@@ -506,35 +599,40 @@ class ScreenParser:
                 frames, elems_all, crops_all, nbox = fut.result()
                 nxt = next(it, None)
                 fut = helper.submit(stage_a, *nxt) if nxt is not None else None
+                ann = None
+                if img is not None:                       # before the caption work, so that it runs under the encode
+                    ann = self._annotate_launch(frames, elems_all, frames[0].shape[1], frames[0].shape[0], draw_bbox_config)
                 with torch.inference_mode(), self.cap._lock:
                     handle = self.caption_launch(frames, crops_all, **({} if prompt is None else {"prompt": prompt}))
                 if pending is not None:
                     yield finish(pending)
-                pending = (handle, elems_all, crops_all, nbox)
+                pending = (handle, elems_all, crops_all, nbox, ann)
             yield finish(pending)
 
-    def _parse_stream_device(self, batches, return_ids, pad_to, prompt=None):
+    def _parse_stream_device(self, batches, return_ids, pad_to, prompt=None, img=None):
         """parse_stream with the device hand-off (the default): four HIP streams, one host thread.  Batch i+1's detector + hand-off
         graph runs on the detector's stream while batch i encodes; its tables are snapshotted (`detect_glue`) so nothing of batch i
         reads the detector plan's buffers afterwards; caption micro-batches alternate between two encode streams (the HBM-bound
         kernels of one fill what the MFMA-bound GEMMs of the other leave idle); batch i's 20 decode steps run on a fourth stream, on
         one of two decode plans, while batch i+1 encodes.  Same kernels on the same data per batch as `parse_batch`."""
         def finish(p):
-            handle, snap, ocr_els, counts, iw, ih, n_frames, n_crops = p
+            handle, snap, ocr_els, counts, iw, ih, n_frames, n_crops = p[:8]
+            early = p[8] if len(p) > 8 else None         # return_image: (elements assembled before the captions, annotate handle)
             with torch.inference_mode(), self.cap._lock:
                 caps = self.caption_finish(handle)
-                elems_all = self.assemble(snap, snap, ocr_els, counts, iw, ih, n_frames)
+                elems_all = early[0] if early is not None else self.assemble(snap, snap, ocr_els, counts, iw, ih, n_frames)
             ids_out = self._fill_captions(elems_all, caps)
             self.stats = {"crops": n_crops, "boxes": [int(v) for v in snap.out_count[:n_frames].tolist()], "split_overflow": getattr(self, "range_overflow_last", 0)}
             self.last_crops = [snap.crops[f, :n].tolist() for f, n in enumerate(n_crops)]
-            return (elems_all, ids_out) if return_ids else elems_all
+            res = (elems_all, ids_out) if return_ids else elems_all
+            return res if early is None else self._with_images(res, return_ids, self._annotate_finish(early[1]))
 
         try:
-            yield from self._stream_loop(batches, return_ids, pad_to, finish, prompt)
+            yield from self._stream_loop(batches, return_ids, pad_to, finish, prompt, *(() if img is None else (img,)))
         finally:
             torch.cuda.synchronize(self.cap.device)      # an abandoned generator leaves no work behind on the side streams
 
-    def _stream_loop(self, batches, return_ids, pad_to, finish, prompt=None):
+    def _stream_loop(self, batches, return_ids, pad_to, finish, prompt=None, img=None):
         pending = None
         for frames, ocr in batches:
             ih, iw = frames[0].shape[:2]
@@ -545,15 +643,23 @@ class ScreenParser:
                 if pending is not None:
                     yield finish(pending)
                     pending = None
-                yield self.parse_batch(frames, ocr, return_ids=return_ids, pad_to=pad_to, **({} if prompt is None else {"prompt": prompt}))
+                yield self.parse_batch(frames, ocr, return_ids=return_ids, pad_to=pad_to, **({} if prompt is None else {"prompt": prompt}),
+                                       **({} if img is None else {"return_image": True, "draw_bbox_config": img[1]}))
                 continue
             snap, _, ocr_els, counts = handed
             n_crops = [int(counts[f, 1]) for f in range(len(frames))]
+            early = ()
+            if img is not None:
+                # the element geometry does not depend on the captions: assemble now and queue overlay + PNG on the annotate stream
+                # BEFORE this batch's caption work, so that it runs under the encode; `finish` fills the captions into these elements
+                with self.det._lock:
+                    elems_all = self.assemble(snap, snap, ocr_els, counts, iw, ih, len(frames))
+                early = ((elems_all, self._annotate_launch(frames, elems_all, iw, ih, img[1])),)
             with torch.inference_mode(), self.cap._lock:
                 handle = self.caption_launch(frames, n_crops, crops_dev=snap.crops, overlap=True, **({} if prompt is None else {"prompt": prompt}))
             if pending is not None:
                 yield finish(pending)
-            pending = (handle, snap, ocr_els, counts, iw, ih, len(frames), n_crops)
+            pending = (handle, snap, ocr_els, counts, iw, ih, len(frames), n_crops, *early)
         if pending is not None:
             yield finish(pending)
 
@@ -564,7 +670,7 @@ class ScreenParser:
         (ref:omnitool/omniparserserver/omniparserserver.py:42-44); the batch route adds this split."""
         ev, out = self._ev, {}
         for name, a, b in (("detect+handoff", "det0", "det1"), ("caption", "cap0", "capE"), ("caption_encode", "cap0", "cap1"),
-                           ("caption_decode", "cap1", "cap2")):
+                           ("caption_decode", "cap1", "cap2"), ("annotate", "ann0", "ann1")):
             if a in ev and b in ev:
                 try:
                     out[name] = round(float(ev[a].elapsed_time(ev[b])), 3)
@@ -584,7 +690,7 @@ class ScreenParser:
             ids_out.append([r for _, r in cl])
         return ids_out
 
-    def _parse_batch_locked(self, frames, ocr, return_ids, iw, ih, pad_to=None, prompt=None):
+    def _parse_batch_locked(self, frames, ocr, return_ids, iw, ih, pad_to=None, prompt=None, return_image=False, draw_bbox_config=None):
         tiled = self.tile_large and (iw > 1952 or ih > 1112)
         pkw = {} if prompt is None else {"prompt": prompt}       # no prompt: the calls they always were (subclasses override `caption`)
         handed = self.detect_glue(frames, ocr, pad_to) if (self.device_glue and not tiled) else None
@@ -592,13 +698,20 @@ class ScreenParser:
             dp, gs, ocr_els, counts = handed
             n_crops = [int(counts[f, 1]) for f in range(len(frames))]
             # crop rectangles were produced on the detector's stream, which the counts read-back above has drained: no event needed
+            ann = None
+            if return_image:                              # geometry is final: overlay + PNG run on their own stream under the captions
+                elems_all = self.assemble(dp, gs, ocr_els, counts, iw, ih, len(frames))
+                ann = self._annotate_launch(frames, elems_all, iw, ih, draw_bbox_config)
             caps = self.caption(frames, n_crops, crops_dev=gs.crops, **pkw)
-            elems_all = self.assemble(dp, gs, ocr_els, counts, iw, ih, len(frames))
+            if not return_image:
+                elems_all = self.assemble(dp, gs, ocr_els, counts, iw, ih, len(frames))
             ids_out = self._fill_captions(elems_all, caps)
+            images = self._annotate_finish(ann) if ann is not None else None
             self.stats = {"crops": n_crops, "boxes": [int(v) for v in dp.out_count[: len(frames)].tolist()], "stage_ms": self.stage_ms(),
                           "split_overflow": getattr(self, "range_overflow_last", 0)}
             self.last_crops = [gs.crops[f, :n].tolist() for f, n in enumerate(n_crops)]
-            return (elems_all, ids_out) if return_ids else elems_all
+            res = (elems_all, ids_out) if return_ids else elems_all
+            return res if ann is None else self._with_images(res, return_ids, images)
         if tiled:
             det_boxes = [self.detect_tiled(f)[0] for f in frames]      # >1080p: overlapping tiles + global NMS (our policy)
         else:
@@ -608,8 +721,10 @@ class ScreenParser:
             texts, boxes = ocr[fi] if ocr is not None else ([], [])
             el, cr = self.glue(xy, iw, ih, boxes, texts)
             elems_all.append(el); crops_all.append(cr)
+        ann = self._annotate_launch(frames, elems_all, iw, ih, draw_bbox_config) if return_image else None
         caps = self.caption(frames, crops_all, **pkw)
         ids_out = self._fill_captions(elems_all, caps)
         self.stats = {"crops": [len(c) for c in crops_all], "boxes": [len(b) for b in det_boxes], "split_overflow": getattr(self, "range_overflow_last", 0)}
         self.last_crops = crops_all            # integer crop boxes per frame, in caption order (parity tests read them)
-        return (elems_all, ids_out) if return_ids else elems_all
+        res = (elems_all, ids_out) if return_ids else elems_all
+        return res if ann is None else self._with_images(res, return_ids, self._annotate_finish(ann))

@@ -101,11 +101,14 @@ class ParseService:
                 continue
             sp = self.screen_parser()
             frames = [torch.from_numpy(np.array(images[i], order="C")).to(sp.det.device) for i in group]
-            elems = sp.parse_batch(frames, [ocrs[i] if ocrs[i] is not None else ([], []) for i in group])
             from .util import utils as U
+            group_ocr = [ocrs[i] if ocrs[i] is not None else ([], []) for i in group]
             if U.overlay_on_device(sp.det.device):
-                pngs = [self._render(images[i], el, fr) for i, el, fr in zip(group, elems, frames)]       # one stream: sequential
+                # overlay + PNG + base64 of the whole group batched on the device, queued under the captions (pipeline.py::_annotate_launch)
+                elems, marked = sp.parse_batch(frames, group_ocr, return_image=True)
+                pngs = [png for png, _ in marked]
             else:
+                elems = sp.parse_batch(frames, group_ocr)
                 pngs = list(self.pool.map(lambda a: self._render(*a), [(images[i], el) for i, el in zip(group, elems)]))
             dt = time.time() - t0
             stage_ms = dict(getattr(sp, "stats", {}).get("stage_ms", {}))      # HIP-event device time per stage of this group's batch

@@ -241,6 +241,50 @@ def render_device(frame, cmds: Sequence[tuple], stream=None):
     return frame
 
 
+def render_device_batch(srcs, dst, cmds_per_frame: Sequence[Sequence[tuple]], stream=None):
+    """`render` of B equal-sized frames in ONE launch (the frame-batched, out-of-place form of OMNI_OP_OVERLAY): `srcs` are B uint8
+    [H,W,3] device tensors, which are only read; `dst` is a uint8 [B,H,W,3] device tensor, every pixel of which is written (a frame
+    without commands is a copy).  The source pointer table, the offset table, the primitive lists of all frames and ONE mask blob
+    (mask offsets absolute in it) travel as a single upload, staged in pinned memory on a GPU so that the copy stays asynchronous
+    on `stream`.  The launch and the upload are queued on `stream` (None: the current one).  Returns the uploaded table, which the
+    caller keeps alive until the launch has run."""
+    import contextlib
+    import torch
+    from .. import _lib as L
+    B = len(srcs)
+    H, W = srcs[0].shape[:2]
+    assert dst.dtype == torch.uint8 and dst.is_contiguous() and tuple(dst.shape) == (B, H, W, 3) and len(cmds_per_frame) == B
+    for f in srcs:
+        assert f.dtype == torch.uint8 and f.is_contiguous() and tuple(f.shape) == (H, W, 3) and f.device == dst.device
+    prims, masks, offs, moff = [], [], [0], 0
+    for cmds in cmds_per_frame:
+        P, M = raster_primitives(cmds)
+        if P.shape[0]:
+            P = P.copy()
+            P[P[:, 0] == PRIM_MASK, 6] += moff
+            prims.append(P)
+            masks.append(M)
+            moff += M.size
+        offs.append(offs[-1] + P.shape[0])
+    n = offs[-1]
+    ptrs = np.asarray([f.data_ptr() for f in srcs], dtype=np.int64)
+    parts = [ptrs.view(np.uint8), np.asarray(offs, dtype=np.int32).view(np.uint8)]
+    o_offs = ptrs.nbytes
+    o_prim = o_offs + 4 * (B + 1)
+    parts += [p.reshape(-1).view(np.uint8) for p in prims]
+    o_mask = o_prim + 32 * n
+    parts += masks if masks else [np.zeros(1, dtype=np.uint8)]
+    host = torch.from_numpy(np.concatenate(parts))
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if dst.is_cuda:
+            host = host.pin_memory()
+        table = host.to(dst.device, non_blocking=True)
+    base = table.data_ptr()
+    L.launch(L.make_op(L.OP_OVERLAY, L.F32, p=[dst.data_ptr(), base + o_prim, base + o_mask, base, base + o_offs],
+                       i={0: H, 1: W, 2: n, 3: B}), stream)
+    return table
+
+
 class BoxAnnotator:
     """ref:util/box_annotator.py:10-44 constructor contract (colour palette fixed to the default one)."""
 

@@ -9,6 +9,7 @@ semantics (App. E of SURVEY.md) and is pinned by golden fixtures generated from 
 source under dependency shims (tests/golden/).
 """
 import base64
+import contextlib
 import io
 import os
 import time
@@ -536,6 +537,87 @@ def annotate_encode_device(image_np: np.ndarray, boxes: torch.Tensor, phrases, d
         n = int(meta[2].item())                        # the one synchronising read: the base64 length decided on the device
         text = b64[:n].cpu().numpy().tobytes()
     return text.decode("ascii"), {f"{phrase}": v for phrase, v in zip(phrases, xywh)}
+
+
+class AnnotateScratch:
+    """Device buffers of the batched overlay + PNG tail for B frames of H x W (about 60 MB per 1080p frame: the annotated frames,
+    the filtered stream, the unit slots, 25 MB of tokens, the PNG and its base64), every one [B][per-frame capacity] as the
+    frame-batched OMNI_OP_PNG_DEFLATE (i5 = 2) lays them out.  A caller that annotates batch after batch keeps one (or two,
+    alternating, when the next batch is queued before this one is read back) instead of allocating per call."""
+
+    def __init__(self, B, H, W, device):
+        u = H * (3 * W + 1)
+        units, units_lz = (u + 4095) // 4096, (u + 32767) // 32768
+        self.B, self.H, self.W = B, H, W
+        self.cap = u + 5 * units + 63
+        nseg = (self.cap - 53 + 4095) // 4096
+        e = lambda shape, dt=torch.uint8: torch.empty(shape, dtype=dt, device=device)
+        self.frames = e((B, H, W, 3))
+        self.png, self.filt, self.slots = e((B, self.cap)), e((B, u)), e((B, units_lz * 33792))
+        self.meta, self.part = e((B, 4 + 2 * units), torch.int32), e((B, 2 * H + nseg), torch.int32)
+        self.b64, self.toks = e((B, 4 * ((self.cap + 2) // 3))), e((B, units_lz * 32768), torch.int32)
+        self.table = None                                  # the last overlay upload (alive until the next launch on this scratch)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.frames, self.png, self.filt, self.slots, self.meta, self.part, self.b64, self.toks))
+
+
+def png_deflate_device_batch(frames_bhwc: torch.Tensor, want_b64=True, stream=None, scratch: Optional[AnnotateScratch] = None):
+    """`png_deflate_device(lz=True)` of B equal-sized frames (uint8 [B,H,W,3], contiguous) in the nine launches of one: the
+    frame-batched OMNI_OP_PNG_DEFLATE (i5 = 2), B times the unit lanes in flight.  Every file is oracle/png_ref.py::deflate_png_lz of
+    its frame.  -> (PNG [B, capacity], base64 [B, 4 ceil(capacity / 3)] or None, meta [B, words]) device tensors, a row per frame:
+    meta[f, 1] = file bytes, meta[f, 2] = base64 bytes of frame f."""
+    assert frames_bhwc.dtype == torch.uint8 and frames_bhwc.is_contiguous() and frames_bhwc.dim() == 4 and frames_bhwc.shape[3] == 3
+    B, H, W = frames_bhwc.shape[:3]
+    sc = scratch if scratch is not None else AnnotateScratch(B, H, W, frames_bhwc.device)
+    assert (sc.B, sc.H, sc.W) == (B, H, W)
+    L.launch(L.make_op(L.OP_PNG_DEFLATE, L.F32,
+                       p=[frames_bhwc.data_ptr(), sc.png.data_ptr(), sc.filt.data_ptr(), sc.slots.data_ptr(), sc.meta.data_ptr(),
+                          sc.part.data_ptr(), sc.b64.data_ptr() if want_b64 else None, sc.toks.data_ptr()],
+                       i={0: H, 1: W, 2: sc.cap, 3: sc.meta.shape[1], 4: sc.part.shape[1], 5: 2, 6: B}), stream)
+    return sc.png, (sc.b64 if want_b64 else None), sc.meta
+
+
+def annotate_encode_device_batch_launch(frames, boxes_per_frame, phrases_per_frame, text_scale=0.4, text_padding=5, text_thickness=2,
+                                        thickness=3, stream=None, scratch: Optional[AnnotateScratch] = None):
+    """Queue `annotate_encode_device` of B equal-sized frames on `stream` (None: the current one) without reading anything back:
+    the layout per frame on the host, ONE overlay launch (out of place: `frames`, uint8 [H,W,3] device tensors, are only read) and
+    ONE deflate chain.  boxes_per_frame: cxcywh ratio tensors; phrases_per_frame: the label-coordinate keys.  -> handle for
+    `annotate_encode_device_batch_finish`."""
+    from .overlay import BoxAnnotator, render_device_batch
+    B = len(frames)
+    h, w = frames[0].shape[:2]
+    ann = BoxAnnotator(text_scale=text_scale, text_padding=text_padding, text_thickness=text_thickness, thickness=thickness)
+    cmds_all, coords = [], []
+    for boxes, phrases in zip(boxes_per_frame, phrases_per_frame):
+        b = boxes * torch.Tensor([w, h, w, h])
+        cx, cy, bw, bh = b.unbind(-1)
+        xyxy = torch.stack((cx - 0.5 * bw, cy - 0.5 * bh, cx + 0.5 * bw, cy + 0.5 * bh), -1).numpy()
+        xywh = torch.stack((cx - 0.5 * bw, cy - 0.5 * bh, bw, bh), -1).numpy()
+        cmds_all.append(ann.plan(xyxy, [f"{i}" for i in range(b.shape[0])], (w, h)))
+        coords.append({f"{phrase}": v for phrase, v in zip(phrases, xywh)})
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        sc = scratch if scratch is not None else AnnotateScratch(B, h, w, frames[0].device)
+        sc.table = render_device_batch(frames, sc.frames, cmds_all, stream)
+        _, b64, meta = png_deflate_device_batch(sc.frames, stream=stream, scratch=sc)
+    return (sc, b64, meta, coords, stream, list(frames))
+
+
+def annotate_encode_device_batch_finish(handle):
+    """-> [(base64 str, label_coordinates)] per frame: ONE synchronising read of the B meta rows (the sizes decided on the device),
+    then the B base64 slices."""
+    sc, b64, meta, coords, stream, _frames = handle
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        sizes = meta[:, :4].cpu()
+        texts = [b64[f, :int(sizes[f, 2])].cpu() for f in range(len(coords))]
+    return [(t.numpy().tobytes().decode("ascii"), c) for t, c in zip(texts, coords)]
+
+
+def annotate_encode_device_batch(frames, boxes_per_frame, phrases_per_frame, **kw):
+    """`annotate_encode_device` for B equal-sized device frames, batched on the device: one overlay launch and one deflate chain for
+    all of them, one read-back of their sizes.  Same layout, pixels, file bytes and label coordinates per frame; the frames
+    themselves are not drawn on.  -> [(base64 str, label_coordinates)]."""
+    return annotate_encode_device_batch_finish(annotate_encode_device_batch_launch(frames, boxes_per_frame, phrases_per_frame, **kw))
 
 
 def get_som_labeled_img(image_source: Union[str, Image.Image], model=None, BOX_TRESHOLD=0.01, output_coord_in_ratio=False,
