@@ -184,7 +184,13 @@ enum {
   /* greedy decoding step (hf:generation/utils.py:2783-2937 + logits_process NoRepeatNGram/ForcedBOS/ForcedEOS):
    *  p0 logits [B,ldl] p1 final_logits_bias f32 or NULL p2 ids i32[B,T] p3 finished i32[B] p6 step i32*
    *  i0 B i1 vocab i2 ldl i3 T i4 max_new_tokens i5 no_repeat_ngram i6 bos i7 eos i8 pad i9 forced_bos(-1)
-   *  i10 forced_eos(-1) i11 increment step afterwards */
+   *  i10 forced_eos(-1) i11 increment step afterwards
+   *  Token scores (additive; p4 NULL = the kernel above, nothing else computed): p4 f32 [B, T] token log-probabilities.  The step that
+   *  writes ids[b][st + 1] also writes p4[b][st + 1] = log_softmax(processed scores)[id] — processed = logits + bias with the
+   *  NoRepeatNGram bans at -inf, i.e. transformers' compute_transition_scores(normalize_logits=True) of its greedy `scores` —
+   *  accumulated in f32 for both logit types; 0 at a forced position (hf's processed row is 0 there and -inf elsewhere) and for a row
+   *  that had finished before the step (it emits pad).  Column 0 (the start token) is never written.  ids, finished and step are
+   *  bit for bit what p4 = NULL writes.  A row without a finite logit (id 0) gets an unspecified value. */
   OMNI_OP_GREEDY_STEP = 16,
   /* crop -> cv2.resize 64x64 INTER_LINEAR -> [Pillow BICUBIC to RxR] -> rescale, normalise
    * (ref:util/utils.py:97-105,120-123 + hf CLIP image processor).

@@ -1886,9 +1886,14 @@ __global__ __launch_bounds__(256) void attn_decode_cross_kernel(DecArgs a, int k
 struct GreedyArgs {
   const void* logits; const float* bias; int* ids; int* finished; const int* step;
   int B, V, ldl, T, max_new, ngram, bos, eos, pad, forced_bos, forced_eos;
+  float* logp;                         // SCORES instantiation only: f32 [B, T] log-probability of every emitted token
 };
 
-template <typename T>
+// SCORES: also write logp[b][st + 1] = log_softmax(processed scores)[tok] — the arg-max IS the row maximum, so that is
+// -log(sum exp(x - max)): a second pass over the row behind the unchanged arg-max (f32 accumulation for both logit types); 0 at a
+// forced position and for a finished row (hf's processed row is 0 / -inf there, and a finished row emits pad).  SCORES = false
+// compiles to the kernel it always was.
+template <typename T, bool SCORES>
 __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs a) {
   __shared__ float sval[256];
   __shared__ int sidx[256];
@@ -1917,6 +1922,7 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs a) {
   if (a.forced_bos >= 0 && cur_len == 1) forced = a.forced_bos;
   if (a.forced_eos >= 0 && cur_len == a.max_new) forced = a.forced_eos;   // max_length - 1 == max_new (start token + max_new)
   int tok;
+  [[maybe_unused]] float lp = 0.0f;
   if (forced >= 0) {
     tok = forced;
   } else {
@@ -1942,11 +1948,26 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs a) {
     // no logit compared greater than -inf: every entry is NaN or -inf (a row nobody asked for, computed from padding, or a diverged
     // input).  torch.argmax returns position 0 then; never hand an out-of-range id to the next step's embedding gather
     if (tok < 0 || tok >= a.V) tok = 0;
+    if constexpr (SCORES) {
+      const float mx = sval[0];                 // the processed row's maximum (-inf for a degenerate row: lp is then unspecified)
+      __syncthreads();                          // every thread holds mx and tok before sval is reused
+      float sum = 0.f;
+      for (int v = threadIdx.x; v < a.V; v += 256) {
+        float x = ldf(lg + v) + (a.bias ? a.bias[v] : 0.0f);
+        for (int q = 0; q < nban; ++q) if (banned[q] == v) x = -INFINITY;
+        sum += expf(x - mx);
+      }
+      sum = wave_sum(sum);
+      if ((threadIdx.x & 63) == 0) sval[threadIdx.x >> 6] = sum;
+      __syncthreads();
+      lp = -logf(((sval[0] + sval[1]) + sval[2]) + sval[3]);
+    }
   }
   if (threadIdx.x == 0) {
     int fin = a.finished[b];
     if (fin) tok = a.pad;                       // finished rows keep emitting pad (hf utils.py:2925-2929)
     ids[st + 1] = tok;
+    if constexpr (SCORES) a.logp[(long long)b * a.T + st + 1] = fin ? 0.0f : lp;
     if (!fin && tok == a.eos) a.finished[b] = 1;
   }
 }
@@ -2481,9 +2502,13 @@ static int launch_greedy(const omni_op_t* op, hipStream_t s) {
   a.B = op->i[0]; a.V = op->i[1]; a.ldl = op->i[2]; a.T = op->i[3]; a.max_new = op->i[4]; a.ngram = op->i[5];
   a.bos = op->i[6]; a.eos = op->i[7]; a.pad = op->i[8]; a.forced_bos = op->i[9]; a.forced_eos = op->i[10];
   OMNI_REQUIRE(a.logits && a.ids && a.finished && a.step && a.B > 0 && a.V > 0 && a.T >= a.max_new + 1, "greedy_step: bad arguments");
-  int rc = by_dtype(op->dtype, "greedy_step",
-      [&] { hipLaunchKernelGGL(greedy_step_kernel<float>, dim3(a.B), dim3(256), 0, s, a); },
-      [&] { hipLaunchKernelGGL(greedy_step_kernel<half_t>, dim3(a.B), dim3(256), 0, s, a); });
+  a.logp = (float*)op->p[4];
+  int rc = a.logp ? by_dtype(op->dtype, "greedy_step",
+      [&] { hipLaunchKernelGGL((greedy_step_kernel<float, true>), dim3(a.B), dim3(256), 0, s, a); },
+      [&] { hipLaunchKernelGGL((greedy_step_kernel<half_t, true>), dim3(a.B), dim3(256), 0, s, a); })
+                  : by_dtype(op->dtype, "greedy_step",
+      [&] { hipLaunchKernelGGL((greedy_step_kernel<float, false>), dim3(a.B), dim3(256), 0, s, a); },
+      [&] { hipLaunchKernelGGL((greedy_step_kernel<half_t, false>), dim3(a.B), dim3(256), 0, s, a); });
   if (rc) return rc;
   if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
   OMNI_HIP_CHECK(hipGetLastError());

@@ -242,6 +242,28 @@ BEAM_MAX = 8                       # include/omni_amd.h OMNI_OP_BEAM_STEP: 2 <= 
 _EARLY_STOPPING_CODE = {False: 0, True: 1, "never": 2}
 
 
+def caption_confidence(ids_row, logp_row, eos, forced_bos, forced_eos, max_new):
+    """Confidence of one greedy caption in (0, 1]: exp of the mean token log-probability — the geometric mean of the probabilities
+    the model gave the tokens it chose — over the generated positions up to and including the first EOS (all of them when there is
+    none).  ids_row: the sequence with the decoder start token at position 0; logp_row: aligned with ids_row[1:]
+    (`generate(output_scores=True).token_logprobs`, `caption_crops(return_scores=True)`); further entries of either are ignored.
+    Forced positions say nothing about the model and are left out: position 1 when forced_bos >= 0, position max_new when
+    forced_eos >= 0.  None when no unforced position remains.  The single host definition (ScreenParser, get_som_labeled_img)."""
+    ids = [int(t) for t in ids_row]
+    lps = [float(v) for v in logp_row]
+    n = min(len(ids) - 1, len(lps), int(max_new))
+    vals = []
+    for p in range(1, n + 1):
+        forced = (forced_bos >= 0 and p == 1) or (forced_eos >= 0 and p == max_new)
+        if not forced:
+            vals.append(lps[p - 1])
+        if ids[p] == eos:
+            break
+    if not vals:
+        return None
+    return float(math.exp(sum(vals) / len(vals)))
+
+
 _DECODE_TUNING = "unset"
 
 
@@ -322,10 +344,14 @@ class _StepPlans:
     cross-attention reads the crop's single cross-K / V row (OMNI_OP_ATTN_DECODE i12 = k), the self-attention reads its history
     through a position table that OMNI_OP_BEAM_STEP rewrites when beams are reordered (no K / V is copied), and OMNI_OP_BEAM_STEP
     replaces OMNI_OP_GREEDY_STEP.  `finished` then holds the per-crop frozen flags (nothing can change any more).  beam = None
-    builds the greedy plan, op for op as before."""
-    beam = None
+    builds the greedy plan, op for op as before.
 
-    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None):
+    scores (greedy only): the plan also owns `logp` f32 [B, T], OMNI_OP_GREEDY_STEP p4 — the log-probability of every emitted token
+    (include/omni_amd.h).  Off, the greedy op keeps p4 = NULL and there is no such buffer."""
+    beam = None
+    logp = None
+
+    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None, scores=False):
         """nkeys: i32 [crops] valid encoder keys per crop (a prompt shorter than the plan's text capacity: OMNI_OP_ATTN_DECODE p7 of
         the cross-attention), or None = all S"""
         w, dev, dt = cap.w, cap.device, cap.dtype
@@ -355,6 +381,8 @@ class _StepPlans:
             self.finished = self.state[3 * crops * kb + crops:]
         else:
             self.finished = pd_.raw((B,), torch.int32)
+        assert not (scores and beam), "token scores are a greedy-decoding output (beam search returns sequences_scores)"
+        self.logp = pd_.raw((B, T), torch.float32) if scores else None
         self.step = pd_.raw((1,), torch.int32)
         esz = 4 if dt == L.F32 else 2
 
@@ -420,7 +448,7 @@ class _StepPlans:
         else:
             pd_.add_op(L.make_op(L.OP_GREEDY_STEP, dt,
                                  p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
-                                    self.finished.data_ptr(), None, None, self.step.data_ptr()],
+                                    self.finished.data_ptr(), self.logp.data_ptr() if scores else None, None, self.step.data_ptr()],
                                  i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: w.bos, 7: w.eos, 8: w.pad,
                                     9: w.forced_bos, 10: w.forced_eos, 11: 1}))
         self.step_flops = pd_.flops
@@ -435,6 +463,8 @@ class _StepPlans:
         self.ids.zero_()
         self.ids[:, 0] = self.start_token
         self.finished.zero_()
+        if self.logp is not None:
+            self.logp.zero_()
         self.step.zero_()
 
     def _reset_beams(self):
@@ -456,6 +486,15 @@ class _StepPlans:
     def result_ids(self, n: int) -> torch.Tensor:
         """device ids of the first n crops: the greedy rows, or the best finished hypothesis of each crop"""
         return self.fin_ids[:n, 0] if self.beam else self.ids[:n]
+
+    def result_logp(self, n: int) -> torch.Tensor:
+        """device token log-probabilities of the first n crops, aligned with `result_ids` (a plan built with scores=True)"""
+        return self.logp[:n]
+
+    def snapshot(self, n: int):
+        """stream-ordered copy of the first n result rows for a later read-back: the ids, or (ids, logp) from a scores plan"""
+        ids = self.result_ids(n).clone()
+        return ids if self.logp is None else (ids, self.result_logp(n).clone())
 
     def _warm_up_and_capture(self, cap, *plans):
         """run the plans once on the captioner's stream (first launches outside a capture), then capture each as a hipGraph"""
@@ -482,7 +521,7 @@ class _DecodePlans(_StepPlans):
     n_txt: text capacity of the micro-batches' plans when the prompt is an input (`_CaptionPlans`); `nkeys` is then the merged
     table of valid encoder keys per crop, copied from the micro-batches like the K / V (`_encode_into`)."""
 
-    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, beam=None, n_txt=None):
+    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, beam=None, n_txt=None, scores=False):
         w, dev, dt = cap.w, cap.device, cap.dtype
         self.B, self.R = B, R
         S = (R // 32) ** 2 + 1 + (len(PROMPT_IDS) if n_txt is None else n_txt)
@@ -497,7 +536,7 @@ class _DecodePlans(_StepPlans):
         # recycled allocator memory there can hold NaN bit patterns, whose logits are all-NaN rows (found by the one-process GPU suite)
         self.cross_kv = [pk.alloc(B, S, 1, 2 * w.d_model, zero=True) for _ in range(w.dec_layers)]
         self._keep = pk.keep
-        self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam, nkeys=self.nkeys)
+        self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam, nkeys=self.nkeys, scores=scores)
         self.free_evt = None       # recorded behind the decode that last used this plan on another stream (pipelined batches)
         self._warm_up_and_capture(cap, self.step_plan)
 
@@ -518,7 +557,7 @@ class _CaptionPlans(_StepPlans):
     pad token's embedding, attend to the valid keys, stay finite) and are read by nobody."""
 
     def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None,
-                 beam=None, n_txt=None):
+                 beam=None, n_txt=None, scores=False):
         w, dev, dt = cap.w, cap.device, cap.dtype
         if arena is not None:
             n_txt = arena.n_txt
@@ -782,7 +821,7 @@ class _CaptionPlans(_StepPlans):
                 self.encode_plan.capture(stream or cap.stream)
             return
         # ---------------- decoder step plan (for a single micro-batch; batches of several micro-batches decode through _DecodePlans)
-        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys)
+        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys, scores=scores)
         self._warm_up_and_capture(cap, self.encode_plan, self.step_plan)
 
     def set_prompt(self, ids: torch.Tensor, nkeys: torch.Tensor, n: int):
@@ -862,6 +901,7 @@ class Florence2Captioner:
         self.max_new_tokens = 20
         self.early_exit_every = 5        # poll the all-rows-finished flag every N decode steps (0 = always run max_new_tokens steps)
         self.num_beams = 1               # caption_crops / ScreenParser: 1 = greedy (the reference's call), k > 1 = beam search
+        self.token_scores = False        # caption_crops / ScreenParser: also return the greedy tokens' log-probabilities / a confidence
         self.last_steps = 0              # decode steps the last `_run` / `_decode_merged` issued
         self._lut, self._bic = None, {}  # crop op tables (`_crop_tables`)
         self._lock = L.DeviceLock(self.device, reentrant=True)   # one caption batch at a time per model; makes this GPU the thread's current device
@@ -976,17 +1016,19 @@ class Florence2Captioner:
         return (k, lp, es)
 
     @torch.inference_mode()
-    def decode_plans(self, B, R, max_new, slot=0, beam=None, n_txt=None) -> _DecodePlans:
+    def decode_plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False) -> _DecodePlans:
         """slot: the pipelined stream (pipeline.py::parse_stream) decodes batch i on its own HIP stream while batch i+1 encodes, so it
         alternates between two decode plans (8 GB of cross-attention K/V each at 384 rows, 768x768 crops).  beam: see
         `beam_config` (B crops = B k decoder rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`)."""
         key = ("dec", B, R, max_new) if slot == 0 else ("dec", B, R, max_new, slot)
         if beam or n_txt is not None:
             key = ("dec", B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
-        return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam, n_txt=n_txt))
+        if scores:                     # token log-probabilities (greedy): a plan set of its own, like a beam configuration
+            key = ("dec", B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),)) + ("scores",)
+        return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
     @torch.inference_mode()
-    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None) -> _CaptionPlans:
+    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False) -> _CaptionPlans:
         """slot 1 = a second, independent set of buffers of the same capacity: the pipelined stream (pipeline.py::parse_stream) keeps two
         128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without).
         beam: see `beam_config` (the step plan decodes B k rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`);
@@ -994,7 +1036,9 @@ class Florence2Captioner:
         key = (B, R, max_new) if slot == 0 else (B, R, max_new, slot)
         if beam or n_txt is not None:
             key = (B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
-        return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam, n_txt=n_txt))
+        if scores:
+            key = (B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),)) + ("scores",)
+        return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
     # ---- prompts
     def prompt_batch(self, rows, R):
@@ -1073,7 +1117,7 @@ class Florence2Captioner:
         for _ in range(max_new):
             run(stream)
         self.last_steps = max_new
-        return dec.result_ids(n).clone()           # stream-ordered snapshot (read back by the caller)
+        return dec.snapshot(n)                     # stream-ordered snapshot (read back by the caller); (ids, logp) from a scores plan
 
     def _lane_stream(self, k):
         # Measured and not kept (round 4, profiles/r4_s2_candidates_ab.txt): CU-masked lane streams (hipExtStreamCreateWithCUMask) and a
@@ -1124,9 +1168,11 @@ class Florence2Captioner:
                 break
         self.last_steps = steps
         if defer:                          # stream-ordered snapshot; the caller reads it back later (no sync here)
-            return cp.result_ids(n).clone()
+            return cp.snapshot(n)
         if cp.beam:                        # finished hypotheses [n, k, T], their scores and generated lengths (synchronises)
             return cp.fin_ids[:n].cpu().long(), cp.fin_score[:n].cpu().clone(), cp.fin_len[:n].cpu().long()
+        if cp.logp is not None:            # (ids, token log-probabilities) of a scores plan
+            return cp.ids[:n].cpu().long(), cp.logp[:n].cpu().clone()
         return cp.ids[:n].cpu().long()     # synchronises the stream
 
     def _finish_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -1159,10 +1205,24 @@ class Florence2Captioner:
         `length_penalty` / `early_stopping` default to the checkpoint's generation settings.  return_dict_in_generate=True returns
         an object with `.sequences` and `.sequences_scores` (hf's beam scores; None for greedy decoding).  The default stays
         num_beams=1 although transformers would take num_beams=3 from Florence-2's generation config: changing it would change what
-        existing callers get.  Sampling is not implemented."""
+        existing callers get.  Sampling is not implemented.
+
+        output_scores=True (greedy decoding, with return_dict_in_generate=True): the returned object gains `.token_logprobs`, f32
+        [B, sequences.shape[1] - 1] aligned with sequences[:, 1:] — the log-probability of every generated token under the processed
+        scores, what transformers' compute_transition_scores(sequences, scores, normalize_logits=True) returns for its greedy
+        `scores`; 0 at forced positions and behind a row's EOS.  It is computed on the device next to the arg-max (OMNI_OP_GREEDY_STEP
+        p4).  hf's `scores` tuple itself (a [B, vocab] tensor per step) is NOT produced: `.scores` does not exist.  With
+        num_beams > 1 it is a ValueError — beam search returns `sequences_scores`."""
         if do_sample:
             raise NotImplementedError("sampling is not implemented (greedy or beam search decoding)")
+        output_scores = kw.pop("output_scores", False)
+        if not isinstance(output_scores, bool):
+            raise ValueError(f"output_scores must be a bool, got {output_scores!r}")
+        if output_scores and not return_dict_in_generate:
+            raise ValueError("output_scores=True needs return_dict_in_generate=True (the scores are a member of the returned object)")
         beam = self.beam_config(num_beams, length_penalty, early_stopping)
+        if output_scores and beam:
+            raise ValueError("output_scores=True is a greedy-decoding output (num_beams=1); beam search returns sequences_scores")
         k = beam[0] if beam else 1
         if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= k:
             raise ValueError(f"num_return_sequences must be in 1..num_beams ({k}), got {num_return_sequences!r}")
@@ -1173,21 +1233,25 @@ class Florence2Captioner:
 
             def fill(cp, s, n):
                 cp.x_in.t[:n, :, :, :3] = pixel_values[s:s + n].to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
-            seq, scores = self._results(self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill, prompt), beam,
-                                        num_return_sequences)
+            parts = self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill, prompt, output_scores)
+            if output_scores:
+                seq, logp = self._results_scores(parts)
+                return SimpleNamespace(sequences=seq, sequences_scores=None, token_logprobs=logp)
+            seq, scores = self._results(parts, beam, num_return_sequences)
         return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
 
-    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None):
+    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False):
         """encode + decode n_all images in chunks of `chunk` on the captioner's stream, each on the plan of its bucket: fill(cp, s, n)
         writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  prompt: `prompt_batch`
-        of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results`."""
+        of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results` (scores: plans that
+        also return the token log-probabilities, for `_results_scores`)."""
         n_txt = prompt[2] if prompt else None
         if src.is_cuda:                                     # pixels / a screenshot the caller is still producing on its own stream
             self.stream.wait_stream(torch.cuda.current_stream(src.device))
         parts = []
         for s in range(0, n_all, chunk):
             n = min(chunk, n_all - s)
-            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam, n_txt=n_txt)
+            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam, n_txt=n_txt, **({"scores": True} if scores else {}))
             with torch.cuda.stream(self.stream):
                 cp.reset()
                 fill(cp, s, n)
@@ -1205,6 +1269,15 @@ class Florence2Captioner:
         T = max(p.shape[1] for p in parts)
         return torch.cat([torch.nn.functional.pad(p, (0, T - p.shape[1]), value=self.w.pad) for p in parts]), None
 
+    def _results_scores(self, parts):
+        """(sequences, token_logprobs [B, T - 1]) of the per-chunk (ids, logp) `_run` results of scores plans: trimmed and padded like
+        `_results`; the log-probabilities of padding are 0"""
+        ids = [self._finish_ids(p[0]) for p in parts]
+        T = max(p.shape[1] for p in ids)
+        seq = torch.cat([torch.nn.functional.pad(p, (0, T - p.shape[1]), value=self.w.pad) for p in ids])
+        logp = torch.cat([torch.nn.functional.pad(p[1][:, 1:i.shape[1]], (0, T - i.shape[1])) for p, i in zip(parts, ids)])
+        return seq, logp.float().contiguous()
+
     def _beam_outputs(self, parts, nrs):
         """hf's output of _beam_search (generation/utils.py:3508-3523) from per-chunk (ids [n,k,T], scores [n,k], lengths [n,k]): the
         best `nrs` hypotheses per image, trimmed to 1 + the longest generated length among the returned ones."""
@@ -1216,13 +1289,20 @@ class Florence2Captioner:
 
     @torch.inference_mode()
     def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None,
-                      prompt_ids=None):
+                      prompt_ids=None, return_scores=None):
         """Fused fast path: crops are cut, resized (cv2-bilinear 64x64, then Pillow-bicubic to R on the
         768 path) and normalised on device from the HBM-resident screenshot (ref:util/utils.py:97-123).
         num_beams: None = `self.num_beams` (default 1, greedy); k > 1 = beam search, the best hypothesis per crop (what
         generate(num_beams=k) returns for the same pixels).
-        prompt_ids: one list of token ids (bos ... eos) for all crops, None = the default PROMPT_IDS; see `prompt_batch`."""
+        prompt_ids: one list of token ids (bos ... eos) for all crops, None = the default PROMPT_IDS; see `prompt_batch`.
+        return_scores: None = `self.token_scores` (default False); True returns (ids, token_logprobs) — f32 [n, ids.shape[1] - 1],
+        aligned with ids[:, 1:], see `generate(output_scores=True)` and `caption_confidence`; greedy decoding only."""
         beam = self.beam_config(num_beams)
+        scores = self.token_scores if return_scores is None else return_scores
+        if not isinstance(scores, bool):
+            raise ValueError(f"return_scores must be a bool or None, got {scores!r}")
+        if scores and beam:
+            raise ValueError("token scores are a greedy-decoding output (num_beams=1); beam search has none")
         prompt = self.prompt_batch([list(prompt_ids)] * len(boxes_px), self.resolution) if prompt_ids is not None and len(boxes_px) else None
         batch_size = max(1, min(int(batch_size), 128))      # plan capacity: buckets stop at 128 crops (the reference's default batch)
 
@@ -1230,9 +1310,12 @@ class Florence2Captioner:
             rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
             self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
         with self._lock:
-            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt)
+            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt, scores)
         if not parts:
-            return torch.zeros((0, 1), dtype=torch.long)
+            ids = torch.zeros((0, 1), dtype=torch.long)
+            return (ids, torch.zeros((0, 0), dtype=torch.float32)) if scores else ids
+        if scores:
+            return self._results_scores(parts)
         return self._results(parts, beam)[0]
 
     # ---- device crop pre-processing (OMNI_OP_CROP_RESIZE), shared by caption_crops and ScreenParser

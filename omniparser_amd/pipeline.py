@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .florence import Florence2Captioner
+from .florence import Florence2Captioner, caption_confidence
 from .util import utils as U
 from .util.yolov9 import YOLOv9Detector
 
@@ -279,10 +279,13 @@ class ScreenParser:
     # ---- stage 3: caption all crops of all frames in packed micro-batches
     @torch.inference_mode()
     def caption(self, frames: Sequence[torch.Tensor], crops_per_frame, max_new_tokens=None, crops_dev: Optional[torch.Tensor] = None,
-                prompt=None):
+                prompt=None, scores=False):
         """crops_per_frame: host rectangles per frame, or — with `crops_dev` (int32 [frames, max_det, 4] on the device, rows in
-        caption order) — just the number of crops per frame: the rectangles then never visit the host.  prompt: see `prompt_ids`."""
-        return self.caption_finish(self.caption_launch(frames, crops_per_frame, max_new_tokens, crops_dev, prompt=prompt))
+        caption order) — just the number of crops per frame: the rectangles then never visit the host.  prompt: see `prompt_ids`.
+        -> per frame a list of (text, ids row) per crop; scores (or a captioner with `token_scores` set): (text, ids row, confidence),
+        `florence.caption_confidence` of the greedy tokens' log-probabilities."""
+        return self.caption_finish(self.caption_launch(frames, crops_per_frame, max_new_tokens, crops_dev, prompt=prompt,
+                                                       **({"scores": True} if scores else {})))
 
     def prompt_ids(self, prompt):
         """one caption prompt for a call: None (the default <CAPTION> prompt), text (a Florence-2 task token or free text, tokenised
@@ -295,12 +298,13 @@ class ScreenParser:
 
     @torch.inference_mode()
     def caption_launch(self, frames: Sequence[torch.Tensor], crops_per_frame, max_new_tokens=None, crops_dev: Optional[torch.Tensor] = None,
-                       overlap=False, prompt=None):
+                       overlap=False, prompt=None, scores=False):
         """queue the crop / encode / decode work of every micro-batch on the captioner's stream; nothing is read back.  The handle
         keeps the frames alive until `caption_finish`.  overlap (parse_stream): micro-batches alternate between `self.encode_lanes`
         HIP streams, and the merged decode runs on a further stream on one of two alternating decode plans, so the next batch's
         encode does not wait for it.  prompt: one prompt for every crop of the call (`prompt_ids`); the default prompt takes the
-        plans it always took."""
+        plans it always took.  scores (or `cap.token_scores`): the decoding plans also write the token log-probabilities
+        (OMNI_OP_GREEDY_STEP p4), snapshotted next to the ids; greedy decoding only.  Off: the plans and the calls they always were."""
         cap = self.cap
         R = cap.resolution
         prompt = self.prompt_ids(prompt)
@@ -333,6 +337,10 @@ class ScreenParser:
         if overlap and merged:
             self._dec_slot = 1 - getattr(self, "_dec_slot", 1)
         bkw = {"beam": beam} if beam else {}
+        if scores or getattr(cap, "token_scores", False):
+            if beam:
+                raise ValueError("caption confidence needs greedy decoding (num_beams = 1): beam search has no token scores")
+            bkw = {"scores": True}     # like the beams: only the plans that decode carry it, the encode-only plans of a merged batch do not change
         dec = cap.decode_plans(cap.decode_bucket(len(flat)), R, max_new_tokens, slot=self._dec_slot if overlap else 0, **bkw, **pkw) if merged else None
         if merged and not overlap:
             with torch.cuda.stream(cap.stream):
@@ -437,17 +445,24 @@ class ScreenParser:
         cap = self.cap
         # single read-back point.  The snapshots were produced on one of the captioner's streams (non-blocking streams: the default
         # stream does not order against them), so the copies are issued ON that stream — stream order alone makes them see the finished ids
+        # (a scores plan's snapshot is (ids, token log-probabilities): both are read here)
         with torch.cuda.stream(ids_stream):
-            ids_all = [t.cpu() for t in ids_all]
-        ids_all = [cap._finish_ids(t.long()) for t in ids_all]
+            ids_all = [tuple(x.cpu() for x in t) if isinstance(t, tuple) else t.cpu() for t in ids_all]
+        logp_all = [t[1] if isinstance(t, tuple) else None for t in ids_all]
+        ids_all = [cap._finish_ids((t[0] if isinstance(t, tuple) else t).long()) for t in ids_all]
         self._check_range()
         self._settle_gc()
         out = [[] for _ in frames]
         k = 0
-        for ids in ids_all:
+        for ids, logp in zip(ids_all, logp_all):
             texts = [t.strip() for t in self.proc.batch_decode(ids, skip_special_tokens=True)]
-            for t, row in zip(texts, ids):
-                out[flat[k][0]].append((t, row))
+            for r, (t, row) in enumerate(zip(texts, ids)):
+                if logp is None:
+                    out[flat[k][0]].append((t, row))
+                else:                      # logp [n, max_new + 1], column 0 = the start token
+                    w = cap.w
+                    out[flat[k][0]].append((t, row, caption_confidence(row, logp[r, 1:], w.eos, w.forced_bos, w.forced_eos,
+                                                                       logp.shape[1] - 1)))
                 k += 1
         return out
 
@@ -537,34 +552,47 @@ class ScreenParser:
 
     @torch.inference_mode()
     def parse_batch(self, frames: Sequence[torch.Tensor], ocr: Optional[Sequence] = None, return_ids=False,
-                    pad_to: Optional[int] = None, prompt=None, return_image=False, draw_bbox_config=None):
+                    pad_to: Optional[int] = None, prompt=None, return_image=False, draw_bbox_config=None, return_confidence=False):
         """frames: uint8 [H,W,3] device tensors (same size); ocr: per frame (texts, xyxy px boxes) or None;
         pad_to: detector plan batch size to use when fewer frames arrive (see `detect`); prompt: the caption prompt of this call
         (`prompt_ids`: text or token ids; None = <CAPTION>).
         return_image: the result gains a LAST member, per frame (som_image_base64, label_coordinates) — the set-of-marks PNG and
         the pixel xywh of every element, the first two members of `get_som_labeled_img`'s result; labels are the running indices of
         the frame's element list, style = draw_bbox_config or util.omniparser.overlay_style((w, h)).  The frames are not drawn on.
-        OMNI_OVERLAY=host: Pillow per frame; OMNI_SKIP_ANNOTATE=1: "" for the image."""
+        OMNI_OVERLAY=host: Pillow per frame; OMNI_SKIP_ANNOTATE=1: "" for the image.
+        return_confidence (or a captioner with `token_scores` set): every element whose `content` the captioner wrote gains
+        "confidence" in (0, 1] (`florence.caption_confidence`: the geometric-mean probability of its greedy tokens, computed on the
+        device next to the arg-max); OCR elements and icons that took OCR text have no such key.  Greedy decoding only."""
         ih, iw = frames[0].shape[:2]
         prompt = self.prompt_ids(prompt)
+        ckw = {"conf": True} if self._confidence(return_confidence) else {}
         with self.det._lock, self.cap._lock:
             if return_image:
-                return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to, prompt, True, draw_bbox_config)
-            return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to, prompt)
+                return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to, prompt, True, draw_bbox_config, **ckw)
+            return self._parse_batch_locked(frames, ocr, return_ids, iw, ih, pad_to, prompt, **ckw)
 
-    def parse_stream(self, batches, return_ids=False, pad_to: Optional[int] = None, prompt=None, return_image=False, draw_bbox_config=None):
+    def _confidence(self, return_confidence) -> bool:
+        if not isinstance(return_confidence, bool):
+            raise ValueError(f"return_confidence must be a bool, got {return_confidence!r}")
+        return return_confidence or bool(getattr(self.cap, "token_scores", False))
+
+    def parse_stream(self, batches, return_ids=False, pad_to: Optional[int] = None, prompt=None, return_image=False, draw_bbox_config=None,
+                     return_confidence=False):
         """Generator over an iterable of (frames, ocr) batches -> what `parse_batch` returns for each, in order, as a software
         pipeline: the detector pass and the host hand-off of batch i+1 run on a helper thread (their stream is the detector's)
         while the captions of batch i occupy the GPU, and the caption work of batch i+1 is queued BEFORE the read-back of batch i
         blocks — the GPU never waits for the host between batches.  Same kernels, same order per batch, same results as
         `parse_batch`.  (Host hand-off only: with OMNI_DEVICE_GLUE the crop table of a batch lives in per-plan device buffers.)
         prompt: one caption prompt for the whole stream (`prompt_ids`).  return_image / draw_bbox_config: as `parse_batch`; the
-        overlay + PNG work of a batch is queued on the annotate stream before its caption work and read back with its ids."""
+        overlay + PNG work of a batch is queued on the annotate stream before its caption work and read back with its ids.
+        return_confidence: as `parse_batch`, for the whole stream."""
         from concurrent.futures import ThreadPoolExecutor
         prompt = self.prompt_ids(prompt)
         img = (True, draw_bbox_config) if return_image else None
+        skw = {"scores": True} if self._confidence(return_confidence) else {}
         if self.device_glue:
-            yield from self._parse_stream_device(batches, return_ids, pad_to, prompt, *(() if img is None else (img,)))
+            yield from self._parse_stream_device(batches, return_ids, pad_to, prompt, *(() if img is None else (img,)),
+                                                 **({"conf": True} if skw else {}))
             return
 
         def stage_a(frames, ocr):
@@ -603,13 +631,13 @@ class ScreenParser:
                 if img is not None:                       # before the caption work, so that it runs under the encode
                     ann = self._annotate_launch(frames, elems_all, frames[0].shape[1], frames[0].shape[0], draw_bbox_config)
                 with torch.inference_mode(), self.cap._lock:
-                    handle = self.caption_launch(frames, crops_all, **({} if prompt is None else {"prompt": prompt}))
+                    handle = self.caption_launch(frames, crops_all, **({} if prompt is None else {"prompt": prompt}), **skw)
                 if pending is not None:
                     yield finish(pending)
                 pending = (handle, elems_all, crops_all, nbox, ann)
             yield finish(pending)
 
-    def _parse_stream_device(self, batches, return_ids, pad_to, prompt=None, img=None):
+    def _parse_stream_device(self, batches, return_ids, pad_to, prompt=None, img=None, conf=False):
         """parse_stream with the device hand-off (the default): four HIP streams, one host thread.  Batch i+1's detector + hand-off
         graph runs on the detector's stream while batch i encodes; its tables are snapshotted (`detect_glue`) so nothing of batch i
         reads the detector plan's buffers afterwards; caption micro-batches alternate between two encode streams (the HBM-bound
@@ -628,11 +656,12 @@ class ScreenParser:
             return res if early is None else self._with_images(res, return_ids, self._annotate_finish(early[1]))
 
         try:
-            yield from self._stream_loop(batches, return_ids, pad_to, finish, prompt, *(() if img is None else (img,)))
+            yield from self._stream_loop(batches, return_ids, pad_to, finish, prompt, *(() if img is None else (img,)),
+                                         **({"conf": True} if conf else {}))
         finally:
             torch.cuda.synchronize(self.cap.device)      # an abandoned generator leaves no work behind on the side streams
 
-    def _stream_loop(self, batches, return_ids, pad_to, finish, prompt=None, img=None):
+    def _stream_loop(self, batches, return_ids, pad_to, finish, prompt=None, img=None, conf=False):
         pending = None
         for frames, ocr in batches:
             ih, iw = frames[0].shape[:2]
@@ -644,7 +673,8 @@ class ScreenParser:
                     yield finish(pending)
                     pending = None
                 yield self.parse_batch(frames, ocr, return_ids=return_ids, pad_to=pad_to, **({} if prompt is None else {"prompt": prompt}),
-                                       **({} if img is None else {"return_image": True, "draw_bbox_config": img[1]}))
+                                       **({} if img is None else {"return_image": True, "draw_bbox_config": img[1]}),
+                                       **({"return_confidence": True} if conf else {}))
                 continue
             snap, _, ocr_els, counts = handed
             n_crops = [int(counts[f, 1]) for f in range(len(frames))]
@@ -656,7 +686,8 @@ class ScreenParser:
                     elems_all = self.assemble(snap, snap, ocr_els, counts, iw, ih, len(frames))
                 early = ((elems_all, self._annotate_launch(frames, elems_all, iw, ih, img[1])),)
             with torch.inference_mode(), self.cap._lock:
-                handle = self.caption_launch(frames, n_crops, crops_dev=snap.crops, overlap=True, **({} if prompt is None else {"prompt": prompt}))
+                handle = self.caption_launch(frames, n_crops, crops_dev=snap.crops, overlap=True, **({} if prompt is None else {"prompt": prompt}),
+                                             **({"scores": True} if conf else {}))
             if pending is not None:
                 yield finish(pending)
             pending = (handle, snap, ocr_els, counts, iw, ih, len(frames), n_crops, *early)
@@ -686,13 +717,19 @@ class ScreenParser:
             q = list(cl)
             for e in el:
                 if e["content"] is None and q:
-                    e["content"] = q.pop(0)[0]
-            ids_out.append([r for _, r in cl])
+                    c = q.pop(0)           # (text, ids row) or, from scores plans, (text, ids row, confidence)
+                    e["content"] = c[0]
+                    if len(c) > 2:
+                        e["confidence"] = c[2]
+            ids_out.append([c[1] for c in cl])
         return ids_out
 
-    def _parse_batch_locked(self, frames, ocr, return_ids, iw, ih, pad_to=None, prompt=None, return_image=False, draw_bbox_config=None):
+    def _parse_batch_locked(self, frames, ocr, return_ids, iw, ih, pad_to=None, prompt=None, return_image=False, draw_bbox_config=None,
+                            conf=False):
         tiled = self.tile_large and (iw > 1952 or ih > 1112)
         pkw = {} if prompt is None else {"prompt": prompt}       # no prompt: the calls they always were (subclasses override `caption`)
+        if conf:
+            pkw["scores"] = True
         handed = self.detect_glue(frames, ocr, pad_to) if (self.device_glue and not tiled) else None
         if handed is not None:
             dp, gs, ocr_els, counts = handed

@@ -159,6 +159,8 @@ def main():
     ap.add_argument("--caption_model_path", default="weights/icon_caption_florence")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--BOX_TRESHOLD", type=float, default=0.05)
+    ap.add_argument("--caption_confidence", action="store_true",
+                    help="captioned icons of parsed_content_list gain \"confidence\" (geometric-mean probability of the greedy tokens)")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
     a = ap.parse_args()

@@ -56,6 +56,13 @@ class Omniparser(object):
             if isinstance(nb, bool) or not isinstance(nb, int) or not 1 <= nb <= 8:
                 raise ValueError(f"caption_num_beams must be an integer in 1..8, got {nb!r}")
             self.caption_model_processor["model"].num_beams = nb
+        # caption_confidence: True = every captioned icon of parsed_content_list gains "confidence" (florence.caption_confidence of the
+        # greedy tokens' log-probabilities, computed on the device next to the arg-max).  Greedy decoding only.
+        if config.get("caption_confidence") is not None:
+            cc = config["caption_confidence"]
+            if not isinstance(cc, bool):
+                raise ValueError(f"caption_confidence must be a bool, got {cc!r}")
+            self.caption_model_processor["model"].token_scores = cc
 
     def _ocr(self, image: Image.Image, ocr=None):
         """`ocr` = (texts, xyxy px boxes) handed over by the caller for THIS image; else the configured provider."""

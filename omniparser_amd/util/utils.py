@@ -403,11 +403,14 @@ def crop_boxes_px(ratio_boxes, W, H):
 
 
 @torch.inference_mode()
-def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_model_processor, prompt=None, batch_size=128):
+def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_model_processor, prompt=None, batch_size=128,
+                            return_confidence=False):
     """ref:util/utils.py:88-132.  Crops are cut/resized/normalised on device and captioned by the HIP
     captioner; `image_source` may be the uint8 HWC numpy image (as in the reference) or a device tensor.
     prompt: the caption prompt of every crop, as the reference's (a Florence-2 task token or free text,
-    `FlorenceProcessor.prompt_ids`); None = `<CAPTION>`."""
+    `FlorenceProcessor.prompt_ids`); None = `<CAPTION>`.
+    return_confidence: (caption, confidence) pairs instead of captions — `florence.caption_confidence` of the greedy tokens'
+    log-probabilities, which the captioner then computes next to its arg-max (`caption_crops(return_scores=True)`)."""
     model, processor = caption_model_processor["model"], caption_model_processor["processor"]
     non_ocr = filtered_boxes[starting_idx:] if starting_idx else filtered_boxes
     H, W = image_source.shape[0], image_source.shape[1]
@@ -418,6 +421,12 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
     img_dev = img_dev.to(model.device)
     # prompt=None / "<CAPTION>": the call it always was (captioners without the keyword keep working); else the processor's ids
     pkw = {} if prompt is None or prompt == "<CAPTION>" else {"prompt_ids": processor.prompt_ids(prompt)}
+    if return_confidence:                    # only when asked for: captioners without the keyword keep working
+        from ..florence import caption_confidence
+        ids, logp = model.caption_crops(img_dev, boxes_px, max_new_tokens=20, batch_size=batch_size, return_scores=True, **pkw)
+        texts = processor.batch_decode(ids, skip_special_tokens=True)
+        w = model.w
+        return [(t.strip(), caption_confidence(r, lp, w.eos, w.forced_bos, w.forced_eos, 20)) for t, r, lp in zip(texts, ids, logp)]
     ids = model.caption_crops(img_dev, boxes_px, max_new_tokens=20, batch_size=batch_size, **pkw)
     texts = processor.batch_decode(ids, skip_special_tokens=True)
     return [t.strip() for t in texts]
@@ -623,8 +632,10 @@ def annotate_encode_device_batch(frames, boxes_per_frame, phrases_per_frame, **k
 def get_som_labeled_img(image_source: Union[str, Image.Image], model=None, BOX_TRESHOLD=0.01, output_coord_in_ratio=False,
                         ocr_bbox=None, text_scale=0.4, text_padding=5, draw_bbox_config=None, caption_model_processor=None,
                         ocr_text=[], use_local_semantics=True, iou_threshold=0.9, prompt=None, scale_img=False, imgsz=None,
-                        batch_size=128):
-    """ref:util/utils.py:417-496 — returns (base64 PNG, label_coordinates, filtered_boxes_elem)."""
+                        batch_size=128, caption_confidence=False):
+    """ref:util/utils.py:417-496 — returns (base64 PNG, label_coordinates, filtered_boxes_elem).
+    caption_confidence (or a caption model with `token_scores` set): every element whose content the captioner wrote gains
+    "confidence", see `florence.caption_confidence`; OCR elements and icons that took OCR text have no such key."""
     if isinstance(image_source, str):
         image_source = Image.open(image_source)
     image_source = image_source.convert("RGB")
@@ -651,11 +662,15 @@ def get_som_labeled_img(image_source: Union[str, Image.Image], model=None, BOX_T
     starting_idx = next((i for i, box in enumerate(elems) if box["content"] is None), -1)
     filtered_boxes = torch.tensor([box["bbox"] for box in elems]).reshape(-1, 4)
     if use_local_semantics:
+        conf = bool(caption_confidence or getattr(caption_model_processor["model"], "token_scores", False))
         parsed = get_parsed_content_icon(filtered_boxes, starting_idx, image_np, caption_model_processor, prompt=prompt,
-                                         batch_size=batch_size)
+                                         batch_size=batch_size, **({"return_confidence": True} if conf else {}))
         for box in elems:
             if box["content"] is None and parsed:
-                box["content"] = parsed.pop(0)
+                if conf:
+                    box["content"], box["confidence"] = parsed.pop(0)
+                else:
+                    box["content"] = parsed.pop(0)
     boxes_cxcywh = _box_convert_xyxy_to_cxcywh(filtered_boxes)
     phrases = [i for i in range(len(boxes_cxcywh))]
     if os.environ.get("OMNI_SKIP_ANNOTATE", "0") == "1":
