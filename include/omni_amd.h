@@ -190,7 +190,15 @@ enum {
    *  NoRepeatNGram bans at -inf, i.e. transformers' compute_transition_scores(normalize_logits=True) of its greedy `scores` —
    *  accumulated in f32 for both logit types; 0 at a forced position (hf's processed row is 0 there and -inf elsewhere) and for a row
    *  that had finished before the step (it emits pad).  Column 0 (the start token) is never written.  ids, finished and step are
-   *  bit for bit what p4 = NULL writes.  A row without a finite logit (id 0) gets an unspecified value. */
+   *  bit for bit what p4 = NULL writes.  A row without a finite logit (id 0) gets an unspecified value.
+   *  Target scores (additive; p5 NULL and p7 NULL = the forms above): a non-NULL p5 turns the step from choosing a token into
+   *  SCORING a given one (teacher forcing) under the RAW model distribution — p5 tlen i32 [B] target lengths, p7 top1 i32 [B, T] or
+   *  NULL, p4 required (p5 with p4 NULL, or p7 without p5: OMNI_E_ARG), p3 neither read nor written (may be NULL), i4 and the
+   *  processors i5 (n-gram ban), i9 (forced bos), i10 (forced eos) ignored, i11 as above.  Row b reads tok = ids[b][st + 1] and never
+   *  writes ids.  If st + 1 <= tlen[b]: p4[b][st + 1] = log_softmax(logits[b] + bias)[tok], accumulated in f32 in ONE pass over the
+   *  row (online maximum / rescaled sum), and p7[b][st + 1] = the row's arg-max (lowest index among equals; 0 for a row without a
+   *  finite logit, as above); otherwise both entries stay as they are (the host zeroes them).  A tok outside 0..vocab-1 scores -inf
+   *  and reads nothing outside the row; a target whose logit is -inf scores -inf, never NaN. */
   OMNI_OP_GREEDY_STEP = 16,
   /* crop -> cv2.resize 64x64 INTER_LINEAR -> [Pillow BICUBIC to RxR] -> rescale, normalise
    * (ref:util/utils.py:97-105,120-123 + hf CLIP image processor).

@@ -122,6 +122,16 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       ext[7] = (long long)i[0] * (3LL * i[6] + 2) * 4;
       break;
     }
+    case OMNI_OP_GREEDY_STEP:                                // the target-score form (p5 / p7): whole buffers; else first bytes, as before
+      if (op->p[5] || op->p[7]) {
+        const long long rows = i[0], T = i[3];
+        ext[0] = rows > 0 ? ((rows - 1) * i[2] + i[1]) * esz : 1;
+        ext[1] = (long long)i[1] * 4;
+        ext[2] = ext[4] = ext[7] = rows * T * 4;
+        ext[5] = rows * 4;
+        ext[6] = 4;
+      }
+      break;
     case OMNI_OP_MLP_FUSED: {
       const long long rows = (long long)i[0] * i[1], C = i[3], hid = i[12];
       ext[0] = span(rows, i[4], i[5], C); ext[1] = hid * C * 4; ext[2] = hid * 4; ext[3] = span(rows, i[16], i[17], C);

@@ -1974,6 +1974,94 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs a) {
 
 __global__ void step_inc_kernel(int* step) { if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1; }
 
+// ------------------------------------------------------------------------------------ score_step (OMNI_OP_GREEDY_STEP p5)
+// Teacher forcing: the token of the step is GIVEN (ids[b][st + 1], read only) and the kernel writes its log-probability under the
+// raw model distribution — log_softmax(logits + bias), no n-gram ban, no forced token — and, optionally, the row's arg-max.
+struct ScoreArgs {
+  const void* logits; const float* bias; const int* ids; const int* step; const int* tlen; float* logp; int* top1;
+  int B, V, ldl, T;
+};
+
+// online log-sum-exp of the entries seen so far: their maximum m, s = sum exp(x - m), i = index of the first maximum.  Nothing seen
+// (or only -inf / NaN, which no comparison admits): m = -inf, s = 0, i = INT_MAX.
+struct OnlineLse { float m, s; int i; };
+
+// entries v .. v + N - 1 (ascending) into r: ONE rescale of the sum per call, and exp(x - m) only of entries above -inf — so neither
+// exp(-inf - -inf) of a row that starts with -inf entries nor a NaN entry reaches the sum (the arg-max skips both as well)
+template <int N>
+__device__ __forceinline__ void lse_take(OnlineLse& r, const float (&x)[N], int v) {
+  float bm = r.m;
+#pragma unroll
+  for (int j = 0; j < N; ++j) if (x[j] > bm) { bm = x[j]; r.i = v + j; }     // first maximum: strict, ascending
+  if (bm > r.m) { r.s *= expf(r.m - bm); r.m = bm; }                           // r.m = -inf: s = 0 stays 0
+#pragma unroll
+  for (int j = 0; j < N; ++j) if (x[j] > -INFINITY) r.s += expf(x[j] - r.m);
+}
+
+// two partial results into one; equal maxima: the lower index
+__device__ __forceinline__ void lse_merge(OnlineLse& r, float om, float os, int oi) {
+  const float nm = fmaxf(r.m, om);
+  if (nm > -INFINITY) r.s = r.s * expf(r.m - nm) + os * expf(om - nm);         // both empty: nothing to rescale (-inf - -inf)
+  if (om > r.m || (om == r.m && oi < r.i)) r.i = oi;
+  r.m = nm;
+}
+
+// One workgroup of 256 per row, ONE pass over the row: 16-byte loads over the aligned middle of the row (a row of ldl = 51289
+// elements is aligned to its element size only: up to kVec - 1 single elements in front and behind), per-thread online
+// (max, sum, arg-max), combined over the wave with shuffles and over the four waves through LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void score_step_kernel(ScoreArgs a) {
+  constexpr int N = ElemTraits<T>::kVec;
+  struct alignas(16) Vec { T v[N]; };
+  __shared__ float sm[4], ss[4];
+  __shared__ int si[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int pos = *a.step + 1;                  // the position scored by this step: ids[b][pos], logp[b][pos], top1[b][pos]
+  if (pos < 1 || pos >= a.T || pos > a.tlen[b]) return;      // uniform per workgroup; behind the row's target: nothing is written
+  const T* lg = (const T*)a.logits + (long long)b * a.ldl;
+  int head = (int)(((16 - ((unsigned long long)lg & 15)) & 15) / sizeof(T));
+  if (head > a.V) head = a.V;
+  const int nvec = (a.V - head) / N, tail = head + nvec * N;
+  OnlineLse r{-INFINITY, 0.0f, 0x7fffffff};
+  if (tid < head) {
+    const float x[1] = {ldf(lg + tid) + (a.bias ? a.bias[tid] : 0.0f)};
+    lse_take<1>(r, x, tid);
+  }
+  for (int q = tid; q < nvec; q += 256) {
+    const int v = head + q * N;
+    const Vec in = *(const Vec*)(lg + v);
+    float x[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = ElemTraits<T>::to_f32(in.v[j]) + (a.bias ? a.bias[v + j] : 0.0f);
+    lse_take<N>(r, x, v);
+  }
+  if (tail + tid < a.V) {
+    const float x[1] = {ldf(lg + tail + tid) + (a.bias ? a.bias[tail + tid] : 0.0f)};
+    lse_take<1>(r, x, tail + tid);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(r.m, o), os = __shfl_xor(r.s, o);
+    const int oi = __shfl_xor(r.i, o);
+    lse_merge(r, om, os, oi);
+  }
+  if ((tid & 63) == 0) { sm[tid >> 6] = r.m; ss[tid >> 6] = r.s; si[tid >> 6] = r.i; }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int w = 1; w < 4; ++w) lse_merge(r, sm[w], ss[w], si[w]);
+  const long long at = (long long)b * a.T + pos;
+  const int tok = a.ids[at];
+  float lp = -INFINITY;                         // a token outside the vocabulary: nothing outside the row is read
+  if (tok >= 0 && tok < a.V) {
+    const float xt = ldf(lg + tok) + (a.bias ? a.bias[tok] : 0.0f);          // the expression of the pass: the same bits
+    if (xt > -INFINITY) lp = (xt - r.m) - logf(r.s);
+    else if (xt != xt) lp = xt;                 // a NaN target stays NaN; a -inf target is -inf even where the whole row is -inf
+  }
+  a.logp[at] = lp;
+  // no entry compared greater than -inf (all NaN / -inf): position 0, as greedy_step_kernel and torch.argmax
+  if (a.top1) a.top1[at] = (r.i < 0 || r.i >= a.V) ? 0 : r.i;
+}
+
 // ------------------------------------------------------------------------------------ beam_step
 // One step of transformers' _beam_search (hf:generation/utils.py:3008-3523, `_get_top_k_continuations`,
 // `_get_running_beams_for_next_iteration`, `_update_finished_beams`, `_check_early_stop_heuristic`) for one crop per workgroup, k beams
@@ -2495,7 +2583,27 @@ static int launch_attn_decode(const omni_op_t* op, hipStream_t s) {
   return OMNI_OK;
 }
 
+// the target-score form of OMNI_OP_GREEDY_STEP (p5 set): p3, i4..i10 are not read
+static int launch_score(const omni_op_t* op, hipStream_t s) {
+  ScoreArgs a{};
+  a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (const int*)op->p[2]; a.logp = (float*)op->p[4];
+  a.tlen = (const int*)op->p[5]; a.step = (const int*)op->p[6]; a.top1 = (int*)op->p[7];
+  a.B = op->i[0]; a.V = op->i[1]; a.ldl = op->i[2]; a.T = op->i[3];
+  OMNI_REQUIRE(a.tlen, "greedy_step: p7 (top1) belongs to the target-score form, which p5 (target lengths) selects");
+  OMNI_REQUIRE(a.logp, "greedy_step: the target-score form (p5) writes p4, which is NULL");
+  OMNI_REQUIRE(a.logits && a.ids && a.step && a.B > 0 && a.V > 0 && a.ldl >= a.V && a.T >= 2, "greedy_step (target scores): bad arguments");
+  OMNI_REQUIRE((unsigned long long)a.logits % (op->dtype == OMNI_F32 ? 4 : 2) == 0, "greedy_step (target scores): logits not aligned to their element");
+  int rc = by_dtype(op->dtype, "greedy_step",
+      [&] { hipLaunchKernelGGL(score_step_kernel<float>, dim3(a.B), dim3(256), 0, s, a); },
+      [&] { hipLaunchKernelGGL(score_step_kernel<half_t>, dim3(a.B), dim3(256), 0, s, a); });
+  if (rc) return rc;
+  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
+  OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
 static int launch_greedy(const omni_op_t* op, hipStream_t s) {
+  if (op->p[5] || op->p[7]) return launch_score(op, s);
   GreedyArgs a{};
   a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (int*)op->p[2]; a.finished = (int*)op->p[3];
   a.step = (const int*)op->p[6];

@@ -264,6 +264,38 @@ def caption_confidence(ids_row, logp_row, eos, forced_bos, forced_eos, max_new):
     return float(math.exp(sum(vals) / len(vals)))
 
 
+FORCE_ROWS = (1, 4, 8)             # candidate rows per crop of a teacher-forced plan (`Florence2Captioner.score`)
+LABEL_CAPACITIES = (8, 16, 32)     # label tokens per candidate (T - 1 of such a plan)
+
+
+def sequence_score(token_logprobs, lengths, labels=None, normalize="mean", forced_bos=None):
+    """Score of whole labels from `Florence2Captioner.score`'s output: the sum (normalize="sum") or the mean ("mean") of each
+    label's token log-probabilities over its own length.  token_logprobs [..., L], lengths [...] -> f64 tensor [...].
+    forced_bos (the checkpoint's `forced_bos_token_id`, `captioner.w.forced_bos`; None or < 0 = none): position 0 is left out when
+    it is that token — generation forces it, so its probability says nothing about the text.  labels ([..., L] ids, or nested lists
+    indexed the same way): position 0 is compared with forced_bos; without labels every label is taken to start with it (what
+    `FlorenceProcessor.prompt_ids` returns does).  A label without a counted position scores 0."""
+    if normalize not in ("mean", "sum"):
+        raise ValueError(f"normalize must be 'mean' or 'sum', got {normalize!r}")
+    lp = torch.as_tensor(token_logprobs).double()
+    ln = torch.as_tensor(lengths).long()
+    pos = torch.arange(lp.shape[-1])
+    counted = pos < ln[..., None]
+    if forced_bos is not None and int(forced_bos) >= 0:
+        if labels is None:
+            skip = torch.ones_like(ln, dtype=torch.bool)
+        else:
+            def firsts(x, depth):                        # the first token of every label, nested as `lengths` is
+                return int(x[0]) if depth == 0 else [firsts(r, depth - 1) for r in x]
+            first = labels[..., 0] if isinstance(labels, torch.Tensor) else torch.tensor(firsts(labels, ln.dim()))
+            skip = torch.as_tensor(first).reshape(ln.shape) == int(forced_bos)
+        counted = counted & ~((pos == 0) & skip[..., None])
+    total = torch.where(counted, lp, torch.zeros_like(lp)).sum(-1)
+    if normalize == "sum":
+        return total
+    return total / counted.sum(-1).clamp(min=1)
+
+
 _DECODE_TUNING = "unset"
 
 
@@ -347,11 +379,19 @@ class _StepPlans:
     builds the greedy plan, op for op as before.
 
     scores (greedy only): the plan also owns `logp` f32 [B, T], OMNI_OP_GREEDY_STEP p4 — the log-probability of every emitted token
-    (include/omni_amd.h).  Off, the greedy op keeps p4 = NULL and there is no such buffer."""
+    (include/omni_amd.h).  Off, the greedy op keeps p4 = NULL and there is no such buffer.
+
+    force = M (no beam, no scores): a teacher-forced plan over B crops x M candidate rows (crop b owns rows [b M, b M + M)) that
+    SCORES given texts instead of generating one.  The cross-attention shares the crop's cross-K / V row (i12 = M) as a beam plan
+    with k = M does, the self-attention has no position table (every row keeps its own cache row), and OMNI_OP_GREEDY_STEP takes
+    its target-score form (p5): `ids` [B M, T] is an INPUT (column 0 the decoder start token, columns 1..len the candidate's
+    labels, `set_targets`), `tlen` i32 [B M] the label lengths (0 = unused row), `logp` f32 / `top1` i32 [B M, T] the outputs.
+    There is no `finished`; max_new is the label capacity T - 1."""
     beam = None
     logp = None
+    force = None
 
-    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None, scores=False):
+    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None, scores=False, force=None):
         """nkeys: i32 [crops] valid encoder keys per crop (a prompt shorter than the plan's text capacity: OMNI_OP_ATTN_DECODE p7 of
         the cross-attention), or None = all S"""
         w, dev, dt = cap.w, cap.device, cap.dtype
@@ -359,7 +399,9 @@ class _StepPlans:
         D, nh, lm = w.d_model, w.n_heads, "model.language_model."
         self.T = max_new + 1
         self.beam = beam
-        kb = beam[0] if beam else 1
+        assert not (force and (beam or scores)), "a teacher-forced plan neither searches nor generates"
+        self.force = force
+        kb = beam[0] if beam else (force or 1)
         crops, B = B, B * kb                               # B = decoder rows from here on
         W = _Weights(cap, PlanBuilder(dev, dt))            # weights / tables missing from the model's cache are uploaded through its builder
         pd_ = PlanBuilder(dev, dt)
@@ -379,10 +421,14 @@ class _StepPlans:
             self.fin_len = self.state[2 * crops * kb:3 * crops * kb].view(crops, kb)
             self.heuristic = self.state[3 * crops * kb:3 * crops * kb + crops]
             self.finished = self.state[3 * crops * kb + crops:]
+        elif force:
+            self.finished = None
+            self.tlen = pd_.raw((B,), torch.int32)
+            self.top1 = pd_.raw((B, T), torch.int32)
         else:
             self.finished = pd_.raw((B,), torch.int32)
         assert not (scores and beam), "token scores are a greedy-decoding output (beam search returns sequences_scores)"
-        self.logp = pd_.raw((B, T), torch.float32) if scores else None
+        self.logp = pd_.raw((B, T), torch.float32) if scores or force else None
         self.step = pd_.raw((1,), torch.int32)
         esz = 4 if dt == L.F32 else 2
 
@@ -423,7 +469,7 @@ class _StepPlans:
                                  p=[dq.ptr, None, None, kv.ptr, da.ptr, kv.ptr + D * esz, None]
                                  + ([nkeys.data_ptr()] if nkeys is not None else []),
                                  i={0: D, 1: 0, 2: 0, 3: 0, 4: 0, 5: D, 6: nh, 7: S, 8: S, 9: D, 10: B, 11: 2 * D,
-                                    **({12: kb} if beam else {})},
+                                    **({12: kb} if beam or kb > 1 else {})},
                                  f={0: 64 ** -0.5}))
             dlinear(pre + "encoder_attn.out_proj", da, dt_, res=xd)
             dln(pre + "encoder_attn_layer_norm", dt_, xd)
@@ -445,6 +491,11 @@ class _StepPlans:
                                  i={0: crops, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: kb, 7: w.eos, 8: w.pad,
                                     9: w.forced_bos, 10: w.forced_eos, 11: 1, 12: _EARLY_STOPPING_CODE[beam[2]]},
                                  f={0: beam[1]}))
+        elif force:                                        # the target-score form: the processors' slots stay empty, p3 is not used
+            pd_.add_op(L.make_op(L.OP_GREEDY_STEP, dt,
+                                 p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(), None,
+                                    self.logp.data_ptr(), self.tlen.data_ptr(), self.step.data_ptr(), self.top1.data_ptr()],
+                                 i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 6: w.bos, 7: w.eos, 8: w.pad, 9: -1, 10: -1, 11: 1}))
         else:
             pd_.add_op(L.make_op(L.OP_GREEDY_STEP, dt,
                                  p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
@@ -459,6 +510,14 @@ class _StepPlans:
     def reset(self):
         if self.beam:
             self._reset_beams()
+            return
+        if self.force:                                     # every row unused (tlen 0) until `set_targets`
+            self.ids.fill_(self.pad_token)
+            self.ids[:, 0] = self.start_token
+            self.tlen.zero_()
+            self.logp.zero_()
+            self.top1.zero_()
+            self.step.zero_()
             return
         self.ids.zero_()
         self.ids[:, 0] = self.start_token
@@ -482,6 +541,12 @@ class _StepPlans:
         self.fin_score.fill_(-1.0e9)
         self.heuristic.fill_(1)
         self.step.zero_()
+
+    def set_targets(self, ids: torch.Tensor, tlen: torch.Tensor):
+        """a force plan's inputs on the current stream: ids i32 [B M, T] (start token, labels, pad) and tlen i32 [B M], from the host"""
+        assert self.force and tuple(ids.shape) == tuple(self.ids.shape) and tuple(tlen.shape) == tuple(self.tlen.shape)
+        self.ids.copy_(ids, non_blocking=True)
+        self.tlen.copy_(tlen, non_blocking=True)
 
     def result_ids(self, n: int) -> torch.Tensor:
         """device ids of the first n crops: the greedy rows, or the best finished hypothesis of each crop"""
@@ -557,7 +622,7 @@ class _CaptionPlans(_StepPlans):
     pad token's embedding, attend to the valid keys, stay finite) and are read by nobody."""
 
     def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None,
-                 beam=None, n_txt=None, scores=False):
+                 beam=None, n_txt=None, scores=False, force=None):
         w, dev, dt = cap.w, cap.device, cap.dtype
         if arena is not None:
             n_txt = arena.n_txt
@@ -821,7 +886,7 @@ class _CaptionPlans(_StepPlans):
                 self.encode_plan.capture(stream or cap.stream)
             return
         # ---------------- decoder step plan (for a single micro-batch; batches of several micro-batches decode through _DecodePlans)
-        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys, scores=scores)
+        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys, scores=scores, force=force)
         self._warm_up_and_capture(cap, self.encode_plan, self.step_plan)
 
     def set_prompt(self, ids: torch.Tensor, nkeys: torch.Tensor, n: int):
@@ -1028,7 +1093,7 @@ class Florence2Captioner:
         return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
     @torch.inference_mode()
-    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False) -> _CaptionPlans:
+    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False, force=None) -> _CaptionPlans:
         """slot 1 = a second, independent set of buffers of the same capacity: the pipelined stream (pipeline.py::parse_stream) keeps two
         128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without).
         beam: see `beam_config` (the step plan decodes B k rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`);
@@ -1038,6 +1103,9 @@ class Florence2Captioner:
             key = (B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
         if scores:
             key = (B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),)) + ("scores",)
+        if force:                      # teacher-forced scoring of `force` candidate rows per crop, max_new = the label capacity
+            key = (B, R, max_new, slot, None) + (() if n_txt is None else (("txt", n_txt),)) + (("force", force, max_new),)
+            return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, n_txt=n_txt, force=force))
         return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
     # ---- prompts
@@ -1317,6 +1385,123 @@ class Florence2Captioner:
         if scores:
             return self._results_scores(parts)
         return self._results(parts, beam)[0]
+
+    # ---- teacher-forced scoring of given texts (OMNI_OP_GREEDY_STEP p5)
+    def _check_labels(self, labels, n):
+        """`score`'s labels -> (per image a list of M token lists, M, shared).  ValueError: no label, an empty label, more than
+        LABEL_CAPACITIES[-1] tokens, an id outside the vocabulary, a per-image list of another length than the images."""
+        tolist = lambda x: x.tolist() if isinstance(x, torch.Tensor) else list(x)
+        labels = [tolist(r) for r in tolist(labels)] if labels is not None else []
+        if not labels:
+            raise ValueError("no labels: at least one candidate text is needed")
+        shared = not (labels[0] and isinstance(labels[0][0], (list, tuple, torch.Tensor)))      # a flat list of ids: one label
+        per = [labels] if shared else [[tolist(r) for r in rows] for rows in labels]
+        if not shared and len(per) != n:
+            raise ValueError(f"{len(per)} label lists for {n} images")
+        vocab = min(self.w.vocab, self.w.sd["model.language_model.shared.weight"].shape[0])     # scored by the lm_head, embedded from the table
+        out = []
+        for rows in per:
+            rows = [[int(t) for t in r] for r in rows]
+            if not rows:
+                raise ValueError("no labels: at least one candidate text is needed")
+            if len(rows) != len(per[0]):
+                raise ValueError("every image needs the same number of labels")
+            for r in rows:
+                if not r:
+                    raise ValueError("an empty label: at least one token is needed")
+                if len(r) > LABEL_CAPACITIES[-1]:
+                    raise ValueError(f"a label of {len(r)} tokens exceeds the limit of {LABEL_CAPACITIES[-1]}")
+                bad = [t for t in r if not 0 <= t < vocab]
+                if bad:
+                    raise ValueError(f"label token id {bad[0]} is outside the vocabulary (0..{vocab - 1})")
+            out.append(rows)
+        return out, len(out[0]), shared
+
+    def _score_chunks(self, src, n_all, chunk, R, per, M, shared, fill, prompt=None):
+        """encode n_all images in chunks of `chunk` and score their M labels: per chunk ONE encode, then one pass of the step plan per
+        FORCE_ROWS[-1] labels (reset of the step state, new ids / lengths, max(length) steps: the host knows them, nothing is polled)."""
+        Lmax = max(len(r) for rows in per for r in rows)
+        cap_l = next(c for c in LABEL_CAPACITIES if Lmax <= c)
+        Mp = next(m for m in FORCE_ROWS if min(M, FORCE_ROWS[-1]) <= m)
+        T = cap_l + 1
+        n_txt = prompt[2] if prompt else None
+        if src.is_cuda:
+            self.stream.wait_stream(torch.cuda.current_stream(src.device))
+        run = (lambda p: p.replay(self.stream)) if self.use_graph else (lambda p: p.run(self.stream))
+        stats = self.score_stats = {"encodes": 0, "passes": 0, "steps": 0}
+        logp = torch.zeros((n_all, M, Lmax), dtype=torch.float32)
+        top1 = torch.zeros((n_all, M, Lmax), dtype=torch.long)
+        for s in range(0, n_all, chunk):
+            n = min(chunk, n_all - s)
+            cp = self.plans(self.bucket(n), R, cap_l, n_txt=n_txt, force=Mp)
+            snaps = []
+            with torch.cuda.stream(self.stream):
+                fill(cp, s, n)
+                if prompt:
+                    cp.set_prompt(prompt[0][s:s + n].to(self.device, non_blocking=True), prompt[1][s:s + n].to(self.device, non_blocking=True), n)
+                run(cp.encode_plan)
+                stats["encodes"] += 1
+                for m0 in range(0, M, Mp):
+                    m1 = min(M, m0 + Mp)
+                    ids = torch.full((cp.B, Mp, T), int(self.w.pad), dtype=torch.int32)
+                    ids[:, :, 0] = int(self.w.start)
+                    tlen = torch.zeros((cp.B, Mp), dtype=torch.int32)
+                    for b in range(n):
+                        for j, r in enumerate((per[0] if shared else per[s + b])[m0:m1]):
+                            ids[b, j, 1:1 + len(r)] = torch.tensor(r, dtype=torch.int32)
+                            tlen[b, j] = len(r)
+                    cp.reset()
+                    cp.set_targets(ids.view(-1, T), tlen.view(-1))
+                    steps = int(tlen.max())
+                    for _ in range(steps):
+                        run(cp.step_plan)
+                    stats["passes"] += 1
+                    stats["steps"] += steps
+                    snaps.append((m0, m1, cp.logp.view(cp.B, Mp, T)[:n, :m1 - m0, 1:1 + Lmax].clone(),
+                                  cp.top1.view(cp.B, Mp, T)[:n, :m1 - m0, 1:1 + Lmax].clone()))
+                for m0, m1, lp, t1 in snaps:             # read back behind the last pass, on the stream that wrote them (synchronises it)
+                    logp[s:s + n, m0:m1] = lp.cpu()
+                    top1[s:s + n, m0:m1] = t1.cpu().long()
+        lengths = torch.tensor([[len(r) for r in (per[0] if shared else per[b])] for b in range(n_all)], dtype=torch.long).view(n_all, M)
+        return SimpleNamespace(token_logprobs=logp, lengths=lengths, top1=top1)
+
+    @torch.inference_mode()
+    def score(self, pixel_values, labels, input_ids=None, attention_mask=None):
+        """How likely are given texts, given an image?  The teacher-forced counterpart of `generate`, what transformers computes with
+        `model(input_ids, pixel_values, labels=labels)`: per image and label the log-probability of every label token under the RAW
+        model distribution log_softmax(logits + final_logits_bias) — no n-gram ban, no forced token (unlike `generate`'s
+        token_logprobs, which follow the processed scores and are 0 at forced positions).
+
+        labels: a list of M token lists shared by all images, or one such list per image.  A label is [bos, ..., eos], exactly what
+        `FlorenceProcessor.prompt_ids(text)` returns and what transformers calls `labels`; the decoder reads
+        shift_tokens_right(labels, pad, decoder_start_token_id).  input_ids / attention_mask: the prompt, as in `generate`.
+        Returns an object with `token_logprobs` f32 [n, M, Lmax] (aligned with the labels, 0 behind a label's end), `lengths`
+        [n, M] and `top1` [n, M, Lmax] (the model's own arg-max at every label position).  See `sequence_score`.
+        The M labels of a crop are rows of one decode over ONE encode (up to 8 at a time; more take further passes of the step
+        loop over the same encoded crops).  ValueError: see `_check_labels`."""
+        with self._lock:
+            Bn, _, R, R2 = pixel_values.shape
+            assert R == R2
+            per, M, shared = self._check_labels(labels, Bn)
+            prompt = self._prompt_from_input_ids(input_ids, attention_mask, Bn, R)
+
+            def fill(cp, s, n):
+                cp.x_in.t[:n, :, :, :3] = pixel_values[s:s + n].to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
+            return self._score_chunks(pixel_values, Bn, 128, R, per, M, shared, fill, prompt)
+
+    @torch.inference_mode()
+    def score_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], labels, prompt_ids=None, batch_size=128):
+        """`score` on the fused path of `caption_crops`: the crops are cut, resized and normalised on the device from the screenshot.
+        labels, result: as `score` (n = len(boxes_px)); prompt_ids: one prompt for all crops, None = PROMPT_IDS."""
+        per, M, shared = self._check_labels(labels, len(boxes_px))
+        prompt = self.prompt_batch([list(prompt_ids)] * len(boxes_px), self.resolution) if prompt_ids is not None and len(boxes_px) else None
+        batch_size = max(1, min(int(batch_size), 128))
+
+        def fill(cp, s, n):
+            rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
+            self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
+        with self._lock:
+            return self._score_chunks(image_u8, len(boxes_px), batch_size, self.resolution, per, M, shared, fill, prompt)
 
     # ---- device crop pre-processing (OMNI_OP_CROP_RESIZE), shared by caption_crops and ScreenParser
     def _crop_tables(self, R):

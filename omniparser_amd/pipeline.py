@@ -287,6 +287,11 @@ class ScreenParser:
         return self.caption_finish(self.caption_launch(frames, crops_per_frame, max_new_tokens, crops_dev, prompt=prompt,
                                                        **({"scores": True} if scores else {})))
 
+    def rank(self, frame: torch.Tensor, elements, queries, top_k=None):
+        """`util.utils.rank_elements` for a frame already on the device: per query the elements of `elements` (one frame's list from
+        `parse_batch`) by descending likelihood of the query as their crop's text, [{"index", "score"}]"""
+        return U.rank_elements(frame, elements, {"model": self.cap, "processor": self.proc}, queries, top_k=top_k)
+
     def prompt_ids(self, prompt):
         """one caption prompt for a call: None (the default <CAPTION> prompt), text (a Florence-2 task token or free text, tokenised
         by the parser's processor) or a list of token ids (bos ... eos) -> list of ids, or None"""

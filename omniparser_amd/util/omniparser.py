@@ -11,6 +11,7 @@ import base64
 import io
 from typing import Callable, Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from PIL import Image
 
@@ -79,6 +80,15 @@ class Omniparser(object):
 
     def parse(self, image_base64: str, ocr=None):
         return self.parse_image(decode_image(image_base64), ocr)
+
+    def ground(self, image_base64: str, queries, top_k=5):
+        """`parse`, then `utils.rank_elements` of the parsed elements: (parsed_content_list, per query the top_k elements as
+        {"index", "score"} by descending likelihood of the query under the caption model).  queries: strings (they need the
+        checkpoint's tokenizer.json) or token-id lists."""
+        image = decode_image(image_base64)
+        _labeled, elements = self.parse_image(image)
+        rankings = U.rank_elements(np.asarray(image.convert("RGB")), elements, self.caption_model_processor, queries, top_k=top_k)
+        return elements, rankings
 
     def parse_many(self, images_base64: Sequence[str]):
         """Service helper: parse several screenshots with the same models (sequentially; the batched device path

@@ -432,6 +432,42 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
     return [t.strip() for t in texts]
 
 
+@torch.inference_mode()
+def rank_elements(image_source, elements, caption_model_processor, queries, top_k=None, prompt=None, normalize="mean"):
+    """Rank the elements of a screenshot by how likely the caption model finds each query as the text of the element's crop ("which
+    element is the save button?"): `Florence2Captioner.score_crops` — one encode per crop, every query a teacher-forced row of the
+    same decode — and `florence.sequence_score`.
+    image_source: the uint8 HWC numpy image or a device tensor; elements: a `parsed_content_list` with ratio bboxes, of any element
+    type; queries: strings (tokenised by the processor's `prompt_ids`: they need the tokenizer.json next to the checkpoint, ValueError
+    without it) or lists of token ids (bos ... eos; always work); prompt: the caption prompt of every crop (None = <CAPTION>).
+    Crops are cut as `crop_boxes_px` cuts them; elements whose crop is empty are skipped.
+    -> per query a list of {"index": position in `elements`, "score"} by descending score (ties: the lower index), cut to top_k."""
+    from ..florence import sequence_score
+    model, processor = caption_model_processor["model"], caption_model_processor["processor"]
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1):
+        raise ValueError(f"top_k must be a positive integer or None, got {top_k!r}")
+    labels = [processor.prompt_ids(q) if isinstance(q, str) else [int(t) for t in q] for q in queries]
+    if not labels:
+        raise ValueError("no queries: at least one is needed")
+    H, W = image_source.shape[0], image_source.shape[1]
+    index, boxes_px = [], []
+    for k, e in enumerate(elements):
+        px = crop_boxes_px([e["bbox"]], W, H)
+        if px:
+            index.append(k)
+            boxes_px.append(px[0])
+    img_dev = image_source if isinstance(image_source, torch.Tensor) else torch.from_numpy(np.array(image_source, order="C"))
+    pkw = {} if prompt is None or prompt == "<CAPTION>" else {"prompt_ids": processor.prompt_ids(prompt) if isinstance(prompt, str) else list(prompt)}
+    out = model.score_crops(img_dev.to(model.device), boxes_px, labels, **pkw)
+    scores = sequence_score(out.token_logprobs, out.lengths, labels=[labels] * len(boxes_px), normalize=normalize,
+                            forced_bos=model.w.forced_bos)
+    ranked = []
+    for j in range(len(labels)):
+        order = sorted(range(len(index)), key=lambda b: (-float(scores[b, j]), index[b]))
+        ranked.append([{"index": index[b], "score": float(scores[b, j])} for b in order][:top_k])
+    return ranked
+
+
 def _box_convert_xyxy_to_cxcywh(b: torch.Tensor) -> torch.Tensor:
     x1, y1, x2, y2 = b.unbind(-1)
     return torch.stack(((x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1), -1)
