@@ -179,12 +179,24 @@ enum {
    *  cache row that holds position t of row b (row b still appends its own k / v at (b, step)); i12 cross-attention rows per
    *  cache row: row b reads kcache / vcache row b / i12 (the k beams of a crop share its one cross-K / V row)
    *  Ragged prompts (additive; NULL = nk_fixed keys everywhere): in cross-attention (i7 > 0, which needs i7 <= i8) p7 is the
-   *  number of valid keys per cache row, i32[ceil(B / i12)], read at b / i12 and clamped to 1..nk_fixed */
+   *  number of valid keys per cache row, i32[ceil(B / i12)], read at b / i12 and clamped to 1..nk_fixed
+   *  Which kernel launches (same slots, same result up to summation order): cross-attention of f32 plans with i0, i1, i11 % 4 == 0
+   *  -> attn_decode_cross_kernel (four waves per (row, head), four keys per 16-byte load).  Self-attention (i7 <= 0) of f32 plans
+   *  without a position table, with i8 (cap) > 64 and i0, i1, i2, i3, i4, i11 % 4 == 0 -> attn_decode_self_kernel, the same mapping on
+   *  keys 0..step; the step's own key / value are taken from p1 / p2, never read back from the cache row appended in the same launch,
+   *  and cache rows beyond `step` are never read.  Everything else (cap <= 64, f16 plans, beam plans, unaligned pitches) -> the generic
+   *  one-wave kernel, which is correct at any cap. */
   OMNI_OP_ATTN_DECODE = 15,
   /* greedy decoding step (hf:generation/utils.py:2783-2937 + logits_process NoRepeatNGram/ForcedBOS/ForcedEOS):
    *  p0 logits [B,ldl] p1 final_logits_bias f32 or NULL p2 ids i32[B,T] p3 finished i32[B] p6 step i32*
    *  i0 B i1 vocab i2 ldl i3 T i4 max_new_tokens i5 no_repeat_ngram i6 bos i7 eos i8 pad i9 forced_bos(-1)
    *  i10 forced_eos(-1) i11 increment step afterwards
+   *  Which kernel launches (same slots, same semantics): greedy_step_kernel keeps the tokens banned by NoRepeatNGram in a list of 32,
+   *  which a history of i4 tokens cannot overflow while i4 - i5 + 1 <= 32 (the n-gram start positions of a full history); with
+   *  i5 > 0 and i4 - i5 + 1 > 32 greedy_step_long_kernel launches instead: the bans go into a bitmap over the vocabulary in LDS
+   *  (((i1 + 31) / 32 + i3) x 4 bytes <= 48 KiB, else OMNI_E_ARG), exact for any history up to T.  Forced tokens, bias, the
+   *  lowest-index tie rule, id 0 for a row without a finite logit, pad for finished rows and p4 are those of greedy_step_kernel, and
+   *  both give bit-identical results on a history the list can hold.  The target-score form (p5) has no ban and one kernel.
    *  Token scores (additive; p4 NULL = the kernel above, nothing else computed): p4 f32 [B, T] token log-probabilities.  The step that
    *  writes ids[b][st + 1] also writes p4[b][st + 1] = log_softmax(processed scores)[id] — processed = logits + bias with the
    *  NoRepeatNGram bans at -inf, i.e. transformers' compute_transition_scores(normalize_logits=True) of its greedy `scores` —

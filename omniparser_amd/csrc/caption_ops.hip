@@ -1725,6 +1725,9 @@ __global__ __launch_bounds__(256) void embed_step_kernel(EmbArgs a) {
 }
 
 // ------------------------------------------------------------------------------------ attn_decode
+// self-attention caches with more rows than this launch attn_decode_self_kernel (f32, no position table, 16-byte aligned pitches);
+// up to 64 keys the generic kernel has one key per lane, so the threshold is never below 64
+constexpr int ATTN_SELF_SPLIT_MIN_CAP = 64;
 struct DecArgs {
   const void* q; const void* knew; const void* vnew; void* kc; void* vc; void* o; const int* step;
   int ldq, qoff, ldn, koff, voff, ldo;    // q [B, ldq]; new k/v rows in [B, ldn]
@@ -1882,6 +1885,91 @@ __global__ __launch_bounds__(256) void attn_decode_cross_kernel(DecArgs a, int k
   }
 }
 
+// Self-attention of a decode step over a LONG history (f32 greedy / teacher-forced plans, no position table, cap > 64).  The generic
+// kernel gives one wave the whole history: every lane fetches its own K row with 64 dword loads and P.V walks the keys one by one —
+// fine at the 21 keys it was written for, 1025 serial iterations per (row, head) on a long plan.  This is the cross kernel's
+// mapping on keys 0..step: four waves per (row, head), each a quarter of the keys, four keys per 16-byte load instruction, eight
+// loads in flight, probabilities through LDS, the four partial outputs summed in wave order.  The step's own key / value come from
+// knew / vnew (registers of the lanes that meet key `step`), never from the cache row that wave 0 appends in the same launch, so
+// no barrier orders the append against the reads.  Cache rows beyond `step` are not read.
+__global__ __launch_bounds__(256) void attn_decode_self_kernel(DecArgs a) {
+  OMNI_DYN_LDS(float, sp);                    // [cap] scores -> probabilities, then 8 reduction slots, then [4][64] partial outputs
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane >> 4, d4 = (lane & 15) * 4;
+  const int st = *a.step, C = a.ldc;
+  if (st < 0 || st >= a.cap) return;          // a step counter beyond the cache (the host never issues one) must not become an address
+  const int nk = st + 1;
+  float* red = sp + ((nk + 3) & ~3);
+  float* part = red + 8;
+  float* Kc = (float*)a.kc + (long long)b * a.cap * C + h * 64 + d4;
+  float* Vc = (float*)a.vc + (long long)b * a.cap * C + h * 64 + d4;
+  const float* kn = (const float*)a.knew + (long long)b * a.ldn + a.koff + h * 64 + d4;
+  const float* vn = (const float*)a.vnew + (long long)b * a.ldn + a.voff + h * 64 + d4;
+  if (wave == 0 && j == 0) *reinterpret_cast<f32x4*>(Kc + (long long)st * C) = *reinterpret_cast<const f32x4*>(kn);
+  if (wave == 0 && j == 1) *reinterpret_cast<f32x4*>(Vc + (long long)st * C) = *reinterpret_cast<const f32x4*>(vn);
+  const f32x4 q = *reinterpret_cast<const f32x4*>((const float*)a.q + (long long)b * a.ldq + a.qoff + h * 64 + d4);
+  const int per = ((nk + 15) >> 4) << 2;      // keys per wave, a multiple of 4
+  const int k0 = wave * per, k1 = min(k0 + per, nk);
+  float mx = -INFINITY;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  for (int kb = k0; kb < k1; kb += 32) {      // eight 4-key loads in flight; all 64 lanes stay in the loop for the shuffles
+    f32x4 kv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = kb + 4 * u + j;
+      const float* src = k == st ? kn : Kc + (long long)k * C;
+      kv[u] = k < k1 ? *reinterpret_cast<const f32x4*>(src) : z4;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = kb + 4 * u + j;
+      float s = (q[0] * kv[u][0] + q[1] * kv[u][1]) + (q[2] * kv[u][2] + q[3] * kv[u][3]);
+      s += __shfl_xor(s, 8); s += __shfl_xor(s, 4); s += __shfl_xor(s, 2); s += __shfl_xor(s, 1);
+      s *= a.scale;
+      if (k < k1) {
+        if ((lane & 15) == 0) sp[k] = s;
+        mx = fmaxf(mx, s);
+      }
+    }
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));      // a wave without keys holds -inf
+  float sum = 0.f;
+  for (int k = tid; k < nk; k += 256) { const float e = expf(sp[k] - mx); sp[k] = e; sum += e; }
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = ((red[4] + red[5]) + red[6]) + red[7];
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int kb = k0; kb < k1; kb += 32) {
+    f32x4 vv[8];
+    float pk[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = kb + 4 * u + j;
+      const bool ok = k < k1;
+      const float* src = k == st ? vn : Vc + (long long)k * C;
+      vv[u] = ok ? *reinterpret_cast<const f32x4*>(src) : z4;
+      pk[u] = ok ? sp[k] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      acc[0] += pk[u] * vv[u][0]; acc[1] += pk[u] * vv[u][1]; acc[2] += pk[u] * vv[u][2]; acc[3] += pk[u] * vv[u][3];
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { acc[e] += __shfl_xor(acc[e], 16); acc[e] += __shfl_xor(acc[e], 32); }
+  if (lane < 16) *reinterpret_cast<f32x4*>(part + wave * 64 + d4) = acc;
+  __syncthreads();
+  if (tid < 64) {
+    const float o = ((part[tid] + part[64 + tid]) + part[128 + tid]) + part[192 + tid];
+    ((float*)a.o)[(long long)b * a.ldo + h * 64 + tid] = o / sum;
+  }
+}
+
 // ------------------------------------------------------------------------------------ greedy_step
 struct GreedyArgs {
   const void* logits; const float* bias; int* ids; int* finished; const int* step;
@@ -1964,6 +2052,98 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs a) {
     }
   }
   if (threadIdx.x == 0) {
+    int fin = a.finished[b];
+    if (fin) tok = a.pad;                       // finished rows keep emitting pad (hf utils.py:2925-2929)
+    ids[st + 1] = tok;
+    if constexpr (SCORES) a.logp[(long long)b * a.T + st + 1] = fin ? 0.0f : lp;
+    if (!fin && tok == a.eos) a.finished[b] = 1;
+  }
+}
+
+// The long-history form: launched when the 32-slot list above could overflow (ngram > 0 and max_new - ngram + 1 > 32 n-gram start
+// positions in a full history).  Same processors, tie rule, clamp, bookkeeping and log-probability; the set of banned tokens is
+// exact for any history up to T.  All 256 threads compare their n-gram start positions with the current prefix and append the
+// followers of the matching ones to a list of capacity T in LDS; the list is then folded into a bitmap over the vocabulary
+// ((V + 31) / 32 words), every thread OR-ing the entries that fall into the words it owns (word w belongs to thread w & 255, so no
+// two threads touch a word and the bitmap does not depend on the order of the list).  Both passes over the row test one bit per
+// entry.  A follower outside 0..V-1 bans nothing, as in the list form (no entry of the row compares equal to it).
+template <typename T, bool SCORES>
+__global__ __launch_bounds__(256) void greedy_step_long_kernel(GreedyArgs a) {
+  OMNI_DYN_LDS(unsigned, bm);          // [(V + 31) / 32] ban bitmap, then [T] followers of the matching n-grams
+  __shared__ float sval[256];
+  __shared__ int sidx[256];
+  __shared__ int nmatch;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int st = *a.step;              // tokens so far = st + 1 (ids[b][0..st]); we write ids[b][st+1]
+  int* ids = a.ids + b * a.T;
+  const int cur_len = st + 1;
+  const int nw = (a.V + 31) >> 5;
+  int* follow = (int*)(bm + nw);
+  for (int w = tid; w < nw; w += 256) bm[w] = 0u;
+  if (tid == 0) nmatch = 0;
+  __syncthreads();
+  // NoRepeatNGram: ban tokens completing an n-gram already generated (incl. decoder start token)
+  const int n = a.ngram;
+  const int nstart = n > 0 && cur_len + 1 >= n ? min(cur_len - n + 1, a.T) : 0;     // start positions i with i + n - 1 < cur_len
+  for (int i = tid; i < nstart; i += 256) {
+    bool match = true;
+    for (int j = 0; j < n - 1; ++j)
+      if (ids[i + j] != ids[cur_len - (n - 1) + j]) { match = false; break; }
+    const int f = ids[i + n - 1];
+    if (match && f >= 0 && f < a.V) follow[atomicAdd(&nmatch, 1)] = f;
+  }
+  __syncthreads();
+  const int nm = nmatch;
+  for (int q = 0; q < nm; ++q) {
+    const int f = follow[q];
+    if (((f >> 5) & 255) == tid) bm[f >> 5] |= 1u << (f & 31);
+  }
+  __syncthreads();
+  int forced = -1;
+  if (a.forced_bos >= 0 && cur_len == 1) forced = a.forced_bos;
+  if (a.forced_eos >= 0 && cur_len == a.max_new) forced = a.forced_eos;   // max_length - 1 == max_new (start token + max_new)
+  int tok;
+  [[maybe_unused]] float lp = 0.0f;
+  if (forced >= 0) {
+    tok = forced;
+  } else {
+    const T* lg = (const T*)a.logits + (long long)b * a.ldl;
+    float best = -INFINITY; int bi = 0x7fffffff;
+    for (int v = tid; v < a.V; v += 256) {
+      float x = ldf(lg + v) + (a.bias ? a.bias[v] : 0.0f);
+      if ((bm[v >> 5] >> (v & 31)) & 1u) x = -INFINITY;
+      if (x > best) { best = x; bi = v; }      // first max within this thread's ascending stride
+    }
+    sval[tid] = best; sidx[tid] = bi;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) {
+        float ov = sval[tid + s]; int oi = sidx[tid + s];
+        if (ov > sval[tid] || (ov == sval[tid] && oi < sidx[tid])) {
+          sval[tid] = ov; sidx[tid] = oi;
+        }
+      }
+      __syncthreads();
+    }
+    tok = sidx[0];
+    // no logit compared greater than -inf (all NaN / -inf): position 0, as greedy_step_kernel and torch.argmax
+    if (tok < 0 || tok >= a.V) tok = 0;
+    if constexpr (SCORES) {
+      const float mx = sval[0];                 // the processed row's maximum (-inf for a degenerate row: lp is then unspecified)
+      __syncthreads();                          // every thread holds mx and tok before sval is reused
+      float sum = 0.f;
+      for (int v = tid; v < a.V; v += 256) {
+        float x = ldf(lg + v) + (a.bias ? a.bias[v] : 0.0f);
+        if ((bm[v >> 5] >> (v & 31)) & 1u) x = -INFINITY;
+        sum += expf(x - mx);
+      }
+      sum = wave_sum(sum);
+      if ((tid & 63) == 0) sval[tid >> 6] = sum;
+      __syncthreads();
+      lp = -logf(((sval[0] + sval[1]) + sval[2]) + sval[3]);
+    }
+  }
+  if (tid == 0) {
     int fin = a.finished[b];
     if (fin) tok = a.pad;                       // finished rows keep emitting pad (hf utils.py:2925-2929)
     ids[st + 1] = tok;
@@ -2570,6 +2750,15 @@ static int launch_attn_decode(const omni_op_t* op, hipStream_t s) {
     OMNI_HIP_CHECK(hipGetLastError());
     return OMNI_OK;
   }
+  if (a.nk_fixed <= 0 && !beam && op->dtype == OMNI_F32 && a.cap > ATTN_SELF_SPLIT_MIN_CAP && a.ldc % 4 == 0 && a.ldq % 4 == 0 &&
+      a.qoff % 4 == 0 && a.ldn % 4 == 0 && a.koff % 4 == 0 && a.voff % 4 == 0) {
+    // self-attention over a long history: the cross kernel's four waves and four keys per load on keys 0..step
+    const size_t lds = (size_t)(((a.cap + 3) & ~3) + 8 + 256) * 4;
+    OMNI_REQUIRE(lds <= 48 * 1024, "attn_decode: %d cache rows exceed the score LDS of the split-key kernel", a.cap);
+    hipLaunchKernelGGL(attn_decode_self_kernel, dim3(a.heads, B), dim3(256), lds, s, a);
+    OMNI_HIP_CHECK(hipGetLastError());
+    return OMNI_OK;
+  }
   dim3 grid(a.heads, B);
   size_t sh = (size_t)nk_max * 4;
   int rc = beam ? by_dtype(op->dtype, "attn_decode",
@@ -2611,6 +2800,21 @@ static int launch_greedy(const omni_op_t* op, hipStream_t s) {
   a.bos = op->i[6]; a.eos = op->i[7]; a.pad = op->i[8]; a.forced_bos = op->i[9]; a.forced_eos = op->i[10];
   OMNI_REQUIRE(a.logits && a.ids && a.finished && a.step && a.B > 0 && a.V > 0 && a.T >= a.max_new + 1, "greedy_step: bad arguments");
   a.logp = (float*)op->p[4];
+  if (a.ngram > 0 && a.max_new - a.ngram + 1 > 32) {
+    // more n-gram start positions in a full history than the list of greedy_step_kernel holds: the exact (bitmap) form
+    const size_t lds = ((size_t)((a.V + 31) >> 5) + (size_t)a.T) * 4;
+    OMNI_REQUIRE(lds <= 48 * 1024, "greedy_step: a vocabulary of %d and %d positions exceed the ban LDS", a.V, a.T);
+    int rl = a.logp ? by_dtype(op->dtype, "greedy_step",
+        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<float, true>), dim3(a.B), dim3(256), lds, s, a); },
+        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<half_t, true>), dim3(a.B), dim3(256), lds, s, a); })
+                    : by_dtype(op->dtype, "greedy_step",
+        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<float, false>), dim3(a.B), dim3(256), lds, s, a); },
+        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<half_t, false>), dim3(a.B), dim3(256), lds, s, a); });
+    if (rl) return rl;
+    if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
+    OMNI_HIP_CHECK(hipGetLastError());
+    return OMNI_OK;
+  }
   int rc = a.logp ? by_dtype(op->dtype, "greedy_step",
       [&] { hipLaunchKernelGGL((greedy_step_kernel<float, true>), dim3(a.B), dim3(256), 0, s, a); },
       [&] { hipLaunchKernelGGL((greedy_step_kernel<half_t, true>), dim3(a.B), dim3(256), 0, s, a); })

@@ -239,6 +239,12 @@ def check_early_stopping(v):
 
 
 BEAM_MAX = 8                       # include/omni_amd.h OMNI_OP_BEAM_STEP: 2 <= k <= 8
+BEAM_STAGING_BYTES = 48 * 1024     # OMNI_OP_BEAM_STEP stages 3 x k x T i32 / f32 positions in LDS
+
+
+def beam_max_new(k: int) -> int:
+    """largest max_new_tokens whose T = max_new_tokens + 1 positions of k beams fit the staging LDS of OMNI_OP_BEAM_STEP"""
+    return BEAM_STAGING_BYTES // (3 * 4 * int(k)) - 1
 _EARLY_STOPPING_CODE = {False: 0, True: 1, "never": 2}
 
 
@@ -948,6 +954,10 @@ class Florence2Captioner:
                               # instead of 176 GB of HBM at the same speed (profiles/r4_s2_candidates_ab.txt).  With it `stage_out[:3]` are
                               # no longer valid after the encode plan: the bisection taps (tools/archive/r3_bisect.py) turn it off
 
+    long_kv_budget_bytes = 2 ** 30   # `generate` / `caption_crops`: the self-attention K / V of one plan (rows x T x d_model x 4 B x 2 x
+                              # decoder layers; 165 MB at 128 rows and T = 35, 4.8 GB at T = 1025) stays under this: longer outputs
+                              # run in chunks of fewer rows (`long_plan_rows`)
+
     def __init__(self, model_dir, device=None, precision: Optional[str] = None, resolution: Optional[int] = None):
         device = L.require_device(device, "Florence2Captioner")
         L.lib()
@@ -987,6 +997,29 @@ class Florence2Captioner:
             if n <= b:
                 return b
         return _BUCKETS[-1]
+
+    # ---- long outputs
+    def max_new_limit(self) -> int:
+        """largest max_new_tokens: the decoder step of generated position p reads row p + 2 of the learned position table"""
+        return int(self.w.sd["model.language_model.decoder.embed_positions.weight"].shape[0]) - 2
+
+    def check_max_new(self, max_new_tokens, beam=None) -> int:
+        """max_new_tokens of `generate` / `caption_crops` / `plans`, or a ValueError naming the limit: an int in 1..rows of the
+        decoder position table - 2; with beam search (beam = `beam_config`) also what OMNI_OP_BEAM_STEP's LDS staging holds."""
+        lim, why = self.max_new_limit(), "the decoder's position table has no row beyond that"
+        if beam and beam_max_new(beam[0]) < lim:
+            lim, why = beam_max_new(beam[0]), f"beam search with num_beams={beam[0]} stages every position of its beams in LDS"
+        n = max_new_tokens
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1 or n > lim:
+            raise ValueError(f"max_new_tokens must be an integer in 1..{lim} ({why}), got {n!r}")
+        return n
+
+    def long_plan_rows(self, max_new_tokens: int, k: int = 1) -> int:
+        """crops per plan for outputs of max_new_tokens: the largest capacity of the bucket ladder whose self-attention K / V
+        (k decoder rows per crop) stays within `long_kv_budget_bytes`, at least the smallest capacity.  128 up to T = 227."""
+        per_row = (int(max_new_tokens) + 1) * self.w.d_model * 4 * 2 * self.w.dec_layers * max(int(k), 1)
+        fit = [b for b in _BUCKETS if b * per_row <= self.long_kv_budget_bytes]
+        return fit[-1] if fit else _BUCKETS[0]
 
     @staticmethod
     def decode_bucket(n: int) -> int:
@@ -1085,6 +1118,7 @@ class Florence2Captioner:
         """slot: the pipelined stream (pipeline.py::parse_stream) decodes batch i on its own HIP stream while batch i+1 encodes, so it
         alternates between two decode plans (8 GB of cross-attention K/V each at 384 rows, 768x768 crops).  beam: see
         `beam_config` (B crops = B k decoder rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`)."""
+        self.check_max_new(max_new, beam)
         key = ("dec", B, R, max_new) if slot == 0 else ("dec", B, R, max_new, slot)
         if beam or n_txt is not None:
             key = ("dec", B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
@@ -1098,6 +1132,7 @@ class Florence2Captioner:
         128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without).
         beam: see `beam_config` (the step plan decodes B k rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`);
         it is part of the cache key, None = the default prompt's plan."""
+        self.check_max_new(max_new, beam)
         key = (B, R, max_new) if slot == 0 else (B, R, max_new, slot)
         if beam or n_txt is not None:
             key = (B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
@@ -1291,6 +1326,7 @@ class Florence2Captioner:
         beam = self.beam_config(num_beams, length_penalty, early_stopping)
         if output_scores and beam:
             raise ValueError("output_scores=True is a greedy-decoding output (num_beams=1); beam search returns sequences_scores")
+        self.check_max_new(max_new_tokens, beam)
         k = beam[0] if beam else 1
         if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= k:
             raise ValueError(f"num_return_sequences must be in 1..num_beams ({k}), got {num_return_sequences!r}")
@@ -1314,6 +1350,7 @@ class Florence2Captioner:
         of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results` (scores: plans that
         also return the token log-probabilities, for `_results_scores`)."""
         n_txt = prompt[2] if prompt else None
+        chunk = min(chunk, self.long_plan_rows(max_new_tokens, beam[0] if beam else 1))     # 128 up to T = 227: as before
         if src.is_cuda:                                     # pixels / a screenshot the caller is still producing on its own stream
             self.stream.wait_stream(torch.cuda.current_stream(src.device))
         parts = []
@@ -1371,6 +1408,7 @@ class Florence2Captioner:
             raise ValueError(f"return_scores must be a bool or None, got {scores!r}")
         if scores and beam:
             raise ValueError("token scores are a greedy-decoding output (num_beams=1); beam search has none")
+        self.check_max_new(max_new_tokens, beam)
         prompt = self.prompt_batch([list(prompt_ids)] * len(boxes_px), self.resolution) if prompt_ids is not None and len(boxes_px) else None
         batch_size = max(1, min(int(batch_size), 128))      # plan capacity: buckets stop at 128 crops (the reference's default batch)
 

@@ -64,6 +64,14 @@ class Omniparser(object):
             if not isinstance(cc, bool):
                 raise ValueError(f"caption_confidence must be a bool, got {cc!r}")
             self.caption_model_processor["model"].token_scores = cc
+        # caption_max_new_tokens: tokens generated per captioned icon (default 20, the reference's call).  With a caption prompt that
+        # asks for more than a label, a larger value gives per-icon descriptions; the captioner refuses what its decoder cannot hold.
+        self.caption_max_new_tokens = 20
+        if "caption_max_new_tokens" in config:
+            mn = config["caption_max_new_tokens"]
+            if isinstance(mn, bool) or not isinstance(mn, int) or mn < 1:
+                raise ValueError(f"caption_max_new_tokens must be an integer >= 1, got {mn!r}")
+            self.caption_max_new_tokens = mn
 
     def _ocr(self, image: Image.Image, ocr=None):
         """`ocr` = (texts, xyxy px boxes) handed over by the caller for THIS image; else the configured provider."""
@@ -75,8 +83,14 @@ class Omniparser(object):
         texts, boxes = self._ocr(image, ocr)
         labeled, _coords, elements = U.get_som_labeled_img(
             image, self.som_model, BOX_TRESHOLD=self.config["BOX_TRESHOLD"], ocr_bbox=boxes, ocr_text=texts,
-            draw_bbox_config=overlay_style(image.size), caption_model_processor=self.caption_model_processor, **_SOM_ARGS)
+            draw_bbox_config=overlay_style(image.size), caption_model_processor=self.caption_model_processor, **_SOM_ARGS,
+            **({"max_new_tokens": self.caption_max_new_tokens} if self.caption_max_new_tokens != 20 else {}))
         return labeled, elements
+
+    def describe(self, image_base64: str, task="<MORE_DETAILED_CAPTION>", max_new_tokens=256):
+        """`utils.describe_image` of the whole screenshot: one description (or, with task="<OCR>", the text) from the caption model
+        alone — no detector, no OCR engine."""
+        return U.describe_image(decode_image(image_base64), self.caption_model_processor, task=task, max_new_tokens=max_new_tokens)
 
     def parse(self, image_base64: str, ocr=None):
         return self.parse_image(decode_image(image_base64), ocr)
