@@ -40,6 +40,25 @@ struct GemmArgs {
   float oscale;                       // 2^-k of the weight pre-scale
 };
 
+// 16-byte row accesses of an epilogue through a buffer descriptor that ends with the last valid row of the tile: the hardware's range
+// check drops a store (and zeroes a load) of a row at or beyond M, in place of a row compare, an exec mask update and 64-bit address
+// arithmetic per access.  The byte offset is the per-lane 32-bit VGPR offset ONLY — the range check does not see a scalar offset.
+#if defined(__AMDGCN__)
+struct RowBuf {
+  __amdgpu_buffer_rsrc_t r;
+  __device__ __forceinline__ RowBuf(const void* base, unsigned bytes) : r(__builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000)) {}
+  __device__ __forceinline__ void store16(unsigned off, f32x4 v) const { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, 0); }
+  __device__ __forceinline__ f32x4 load16(unsigned off) const { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0)); }
+};
+#else   // host pass / host emulation: the same range check in plain C++
+struct RowBuf {
+  unsigned char* base; unsigned bytes;
+  RowBuf(const void* b, unsigned n) : base((unsigned char*)b), bytes(n) {}
+  void store16(unsigned off, f32x4 v) const { if (off + 16u <= bytes) *reinterpret_cast<f32x4*>(base + off) = v; }
+  f32x4 load16(unsigned off) const { return off + 16u <= bytes ? *reinterpret_cast<const f32x4*>(base + off) : f32x4{0.f, 0.f, 0.f, 0.f}; }
+};
+#endif
+
 // Epilogue shared by the kernels below.
 // D^T layout: lane -> token (lane & 31) of each token tile; accumulator quad q of channel tile j holds
 // channels j*32 + 8q + 4*(lane >> 5) + 0..3.  A lane therefore owns 16-byte pieces of 32 different rows: stored directly, one
@@ -47,7 +66,10 @@ struct GemmArgs {
 // read-heavy ones streamed at 5.1, profiles/r3_s2b_caption_per_op.txt).  So each wave transposes one 32-row token tile at a time
 // through its own slice of the (now idle) LDS ring: rows are assembled in LDS exactly as they lie in memory (f32, or format B as
 // two 8-byte halves), then 16 lanes read one row's 256 bytes and store them contiguously — 4 rows x 256 B per instruction; the
-// residual is added after the transposition, from equally coalesced loads.
+// residual is added after the transposition, from equally coalesced loads.  Output and residual are addressed through tile-relative
+// RowBuf descriptors (base = first row of the tile and first channel of the wave, like rsrcA / rsrcB: a stage-0 output exceeds 4 GB)
+// that end with the wave's last channel of row min(M, m0 + BM) - 1.  2^-k is a power of two, so acc * 2^-k is exact and ONE fma
+// gives the bits of multiply + add (outside the subnormal range).
 template <int BM, int BN, int WM, int WN, int TM, int TN, int LDS_BYTES, int ACT, bool OSPLIT, bool RES>
 __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& a, unsigned char* lds, int m0, int n0, int wave, int lane) {
   constexpr int NW = WM * WN;
@@ -61,6 +83,12 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
   const float osc = a.oscale;
   float amax = 0.0f;                                         // range guard of the split output (omni_internal.h)
   const int rrow = lane >> 4, chunk = lane & 15;             // read phase: 16 lanes per row, 16 bytes per lane
+  const int trows = min(a.M - m0, BM), wc0 = n0 + wn * (BN / WN);   // valid rows of the tile (>= 1), first channel of this wave
+  const RowBuf ybuf(a.y + ((long long)m0 * a.ldo + a.out_coff + wc0) * 4, (unsigned)(trows - 1) * (unsigned)(a.ldo * 4) + (BN / WN) * 4);
+  const RowBuf rbuf(RES ? reinterpret_cast<const unsigned char*>(a.res) + ((long long)m0 * a.ldr + a.res_coff + wc0) * 4 : a.y,
+                    RES ? (unsigned)(trows - 1) * (unsigned)(a.ldr * 4) + (BN / WN) * 4 : 0u);
+  const unsigned yoff = (unsigned)(wm * (BM / WM) + rrow) * (unsigned)(a.ldo * 4) + chunk * 16;   // row rrow of this wave's first token tile
+  const unsigned roff = (unsigned)(wm * (BM / WM) + rrow) * (unsigned)(a.ldr * 4) + chunk * 16;
   static_assert(!(RES && OSPLIT), "residual + format-B output is not a layer of this model");
 #pragma unroll
   for (int jh = 0; jh < TN / 2; ++jh) {
@@ -72,12 +100,9 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
       for (int q = 0; q < 4; ++q)
         bq[j][q] = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + nw0 + 4 * hsel + j * 32 + q * 8) : f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 rres[8];
-    auto load_res = [&](int i) {                             // residual rows of token tile i in the read-phase layout (rows clamped: M tail)
+    auto load_res = [&](int i) {                             // residual rows of token tile i in the read-phase layout (rows >= M read as 0)
 #pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int m = min(m0 + wm * (BM / WM) + i * 32 + it * 4 + rrow, a.M - 1);
-        rres[it] = *reinterpret_cast<const f32x4*>(a.res + (long long)m * a.ldr + a.res_coff + nw0 + chunk * 4);
-      }
+      for (int it = 0; it < 8; ++it) rres[it] = rbuf.load16(roff + (unsigned)(i * 32 + it * 4) * (unsigned)(a.ldr * 4) + jh * 256);
     };
     if constexpr (RES) load_res(0);
 #pragma unroll
@@ -92,15 +117,15 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
           if constexpr (ACT == OMNI_ACT_GELU) {              // two elements per packed instruction
 #pragma unroll
             for (int c = 0; c < 4; c += 2) {
-              const f32x2 g = omni_gelu2(f32x2{ac[q * 4 + c], ac[q * 4 + c + 1]} * osc + f32x2{bq[j][q][c], bq[j][q][c + 1]});
+              const f32x2 g = omni_gelu2(__builtin_elementwise_fma(f32x2{ac[q * 4 + c], ac[q * 4 + c + 1]}, (f32x2)osc, f32x2{bq[j][q][c], bq[j][q][c + 1]}));
               v[c] = g[0]; v[c + 1] = g[1];
             }
           } else {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              float t = ac[q * 4 + c] * osc + bq[j][q][c];
-              if constexpr (ACT == OMNI_ACT_SILU) t = t / (1.0f + expf(-t));
-              v[c] = t;
+            for (int c = 0; c < 4; c += 2) {
+              f32x2 t = __builtin_elementwise_fma(f32x2{ac[q * 4 + c], ac[q * 4 + c + 1]}, (f32x2)osc, f32x2{bq[j][q][c], bq[j][q][c + 1]});
+              if constexpr (ACT == OMNI_ACT_SILU) t = f32x2{t[0] / (1.0f + expf(-t[0])), t[1] / (1.0f + expf(-t[1]))};
+              v[c] = t[0]; v[c + 1] = t[1];
             }
           }
           const int cl = j * 32 + q * 8 + 4 * hsel;          // channel within the pass's 64
@@ -114,7 +139,6 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
           }
         }
       OMNI_WAVE_SYNC();
-      const int mt0 = m0 + wm * (BM / WM) + i * 32;
       f32x4 ov[8];
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
@@ -123,11 +147,10 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
       }
       if constexpr (RES) { if (i + 1 < TM) load_res(i + 1); }  // next tile's residual rows: in flight under the stores and the next tile's arithmetic
 #pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int m = mt0 + it * 4 + rrow;
-        if (m < a.M) *reinterpret_cast<f32x4*>(a.y + ((long long)m * a.ldo + a.out_coff + nw0) * 4 + chunk * 16) = ov[it];
-      }
+      for (int it = 0; it < 8; ++it) ybuf.store16(yoff + (unsigned)(i * 32 + it * 4) * (unsigned)(a.ldo * 4) + jh * 256, ov[it]);
       OMNI_WAVE_SYNC();                                      // the next token tile overwrites the staging rows
+      __builtin_amdgcn_sched_barrier(0);                     // one token tile at a time: without branches around the stores the scheduler would
+                                                             // otherwise hoist later tiles' loads and arithmetic and raise the register count
     }
   }
   if constexpr (OSPLIT) omni_report_range(amax);
@@ -543,8 +566,8 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_kernel(MlpArgs a) {
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
-          const f32x2 t = omni_gelu2((f32x2{a1[0][q * 4 + r], a1[0][q * 4 + r + 1]} + f32x2{a1[1][q * 4 + r], a1[1][q * 4 + r + 1]}) * osc1 +
-                                     f32x2{bq[r], bq[r + 1]});
+          const f32x2 t = omni_gelu2(__builtin_elementwise_fma(f32x2{a1[0][q * 4 + r], a1[0][q * 4 + r + 1]} + f32x2{a1[1][q * 4 + r], a1[1][q * 4 + r + 1]},
+                                                               (f32x2)osc1, f32x2{bq[r], bq[r + 1]}));
           v[r] = t[0]; v[r + 1] = t[1];
         }
         omni_split4(v, hq[qq], lq[qq], amax);
@@ -586,6 +609,8 @@ int launch_tile(GemmArgs& a, int act, int osplit, hipStream_t s) {
   // 256x256 tile: the ping-pong schedule (SCHED 2, round 6: -3.4 / -2.5 / -4.2 % on fc2 / fc1 / qkv of DaViT stage 2, bit-identical
   // results; 641 instead of 654-662 ms per bench step) unless OMNI_GEMM_SCHED=1 asks for the lockstep schedule (the A/B knob of
   // tools/gemm_exp.py sched and of tests/gpu_checks.py::check_gemm_schedules_bitwise)
+  // read per launch on purpose: check_gemm_schedules_bitwise switches the variable between launches of one process (a value cached at the
+  // first launch would make it compare the ping-pong schedule with itself); graph replays never come here
   const char* sched_e = getenv("OMNI_GEMM_SCHED");
   const bool lockstep = sched_e && atoi(sched_e) == 1;
 #define OMNI_GD(ACT_, OS_, RES_)                                                                                                   \
@@ -634,7 +659,8 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE(a.ldi % 16 == 0 && a.in_coff % 16 == 0, "gemm_dma: split input needs 16-channel aligned ld / offset (%d, %d)", a.ldi, a.in_coff);
   OMNI_REQUIRE(a.ldo % 4 == 0 && a.out_coff % 4 == 0 && (!osplit || (a.ldo % 16 == 0 && a.out_coff % 16 == 0)), "gemm_dma: output alignment");
   OMNI_REQUIRE(!a.res || (a.ldr % 4 == 0 && a.res_coff % 4 == 0), "gemm_dma: residual alignment");
-  OMNI_REQUIRE((long long)a.ldi * 4 * 256 < (1ll << 31) && (long long)a.K * 4 * 256 < (1ll << 31), "gemm_dma: row stride too large");
+  OMNI_REQUIRE((long long)a.ldi * 4 * 256 < (1ll << 31) && (long long)a.K * 4 * 256 < (1ll << 31) && (long long)a.ldo * 4 * 256 < (1ll << 31) &&
+               (long long)a.ldr * 4 * 256 < (1ll << 31), "gemm_dma: row stride too large");
   a.nk = a.K / 32;
   // tile choice: 256x256 (one 8-wave block per CU, 128x64 per wave) when N allows, 256x128 otherwise — as long as the launch
   // still has a block for every CU; a short token matrix (small caption batches, 64x64 crops) takes 128x128 tiles instead, which
@@ -691,6 +717,7 @@ int omni_launch_mlp_fused(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE(M > 0 && M < (1ll << 31), "mlp_fused: bad row count");
   OMNI_REQUIRE(a.ldi % 16 == 0 && a.in_coff % 16 == 0, "mlp_fused: split input needs 16-channel aligned ld / offset");
   OMNI_REQUIRE(a.ep.ldo % 4 == 0 && a.ep.out_coff % 4 == 0 && a.ep.ldr % 4 == 0 && a.ep.res_coff % 4 == 0, "mlp_fused: output / residual alignment");
+  OMNI_REQUIRE((long long)a.ep.ldo * 4 * 128 < (1ll << 31) && (long long)a.ep.ldr * 4 * 128 < (1ll << 31), "mlp_fused: row stride too large");
   a.ep.M = (int)M; a.ep.N = C; a.ep.K = HID; a.ep.nk = 0; a.ep.ldi = 0; a.ep.in_coff = 0;
   a.ep.mtiles = a.ep.ntiles = a.ep.xcd_order = a.ep.xcd_n = 0;
   hipLaunchKernelGGL((mlp_fused_kernel<128, 512>), dim3((unsigned)((M + 127) / 128)), dim3(256), 0, s, a);

@@ -112,8 +112,12 @@ __device__ __forceinline__ void omni_split4_raw(const float* v, uint2& hi, uint2
   for (int e = 0; e < 4; ++e) c[e] = __builtin_fminf(__builtin_fmaxf(v[e], -OMNI_F16_MAX), OMNI_F16_MAX);
   hv2 h01 = __builtin_amdgcn_cvt_pkrtz(c[0], c[1]);
   hv2 h23 = __builtin_amdgcn_cvt_pkrtz(c[2], c[3]);
-  hv2 l01 = __builtin_amdgcn_cvt_pkrtz(c[0] - (float)h01[0], c[1] - (float)h01[1]);
-  hv2 l23 = __builtin_amdgcn_cvt_pkrtz(c[2] - (float)h23[0], c[3] - (float)h23[1]);
+  // x - hi is exact in f32 (hi is x truncated to 11 significant bits), so the fused form gives the same bits as convert + subtract; it
+  // compiles to one mixed-precision fma that reads the half directly
+  float m1 = -1.0f;
+  asm("" : "+r"(m1));                             // opaque to the optimiser, which would turn fma(h, -1, x) back into convert + subtract
+  hv2 l01 = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)h01[0], m1, c[0]), __builtin_fmaf((float)h01[1], m1, c[1]));
+  hv2 l23 = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)h23[0], m1, c[2]), __builtin_fmaf((float)h23[1], m1, c[3]));
   hi.x = __builtin_bit_cast(unsigned, h01); hi.y = __builtin_bit_cast(unsigned, h23);
   lo.x = __builtin_bit_cast(unsigned, l01); lo.y = __builtin_bit_cast(unsigned, l23);
 }
@@ -165,29 +169,40 @@ __device__ __forceinline__ float omni_erff(float a) {
   return t > 0.927734375f ? big : small;
 }
 __device__ __forceinline__ float omni_gelu(float v) { return 0.5f * v * (1.0f + omni_erff(v * 0.70710678118654752440f)); }
-// the same arithmetic on two elements at once: every multiply / add / fma is a packed v_pk_*_f32 (full rate on gfx950), which halves
-// the instruction count of the GEMM epilogues once more; bit-identical to two omni_gelu calls
+// GELU of the GEMM epilogues, two elements per packed v_pk_*_f32 instruction (full rate on gfx950).  Those epilogues run with the
+// matrix pipe idle, so every instruction here is wall time; this form evaluates ONE polynomial and no select:
+//   t = min(|v|, 6 sqrt 2),  E = exp2(p(t)) ~ erfc(t / sqrt 2),  1 + erf(v / sqrt 2) = E for v < 0 and 2 - E otherwise, so
+//   gelu(v) = v * (c0 - c1 * E)  with  c1 = copysign(0.5, v),  c0 = 0.5 + c1  (1 or 0).
+// For v < 0 nothing cancels (the two-polynomial omni_gelu above returns 0 below v = -5.6 and loses digits from v = -1 on); for v > 0
+// an absolute error of E is a relative error of the same size in the result.  p is a degree-11 weighted minimax fit of
+// log2 erfc(|v| / sqrt 2) on [0, 6 sqrt 2] (log2 e and 1 / sqrt 2 folded in; tools/fit_gelu_erfc.py: Lawson iteration in float64, error
+// of E 1.3e-8).  Evaluated in f32 Horner form as below, against a float64 GELU on the samples of tests/test_gelu_onebranch_cpu.py:
+// max abs 3.84e-7, max rel 5.5e-4 where the reference is a normal number (omni_gelu: 4.47e-7, 1.0).  21 instructions per pair with the
+// bias fma of the caller (tools/gemm_epilogue_isa.py), 33 for the packed two-polynomial form it replaced.
+// The halving of 0.5 * v * (1 + erf) sits in c0 / c1: halving commutes with rounding outside the subnormal range, so v * fma(0.5, e, 0.5)
+// already had the bits of (0.5 * v) * (1 + e) for the two-polynomial e (compared bitwise in the same test).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+#if defined(__AMDGCN__)
+#define OMNI_EXP2(x) __builtin_amdgcn_exp2f(x)     // bare v_exp_f32: the argument is in [-56, 0]
+#else
+#define OMNI_EXP2(x) __builtin_exp2f(x)
+#endif
 __device__ __forceinline__ f32x2 omni_gelu2(f32x2 v) {
-  const f32x2 a = v * 0.70710678118654752440f;
-  const f32x2 t = __builtin_elementwise_min(__builtin_elementwise_abs(a), (f32x2)6.0f), s = t * t;
-  f32x2 r = __builtin_elementwise_fma((f32x2)-1.72853470e-5f, t, (f32x2)3.83197126e-4f);
-  const f32x2 u = __builtin_elementwise_fma((f32x2)-3.88396438e-3f, t, (f32x2)2.42546219e-2f);
-  r = __builtin_elementwise_fma(r, s, u);
-  r = __builtin_elementwise_fma(r, t, (f32x2)-1.06777847e-1f);
-  r = __builtin_elementwise_fma(r, t, (f32x2)-6.34846687e-1f);
-  r = __builtin_elementwise_fma(r, t, (f32x2)-1.28717512e-1f);
-  r = __builtin_elementwise_fma(r, t, -t);
-  f32x2 big = {1.0f - __expf(r[0]), 1.0f - __expf(r[1])};
-  big = __builtin_elementwise_copysign(big, a);
-  f32x2 q = __builtin_elementwise_fma((f32x2)-5.96761703e-4f, s, (f32x2)4.99119423e-3f);
-  q = __builtin_elementwise_fma(q, s, (f32x2)-2.67681349e-2f);
-  q = __builtin_elementwise_fma(q, s, (f32x2)1.12819925e-1f);
-  q = __builtin_elementwise_fma(q, s, (f32x2)-3.76125336e-1f);
-  q = __builtin_elementwise_fma(q, s, (f32x2)1.28379166e-1f);
-  const f32x2 small = __builtin_elementwise_fma(q, a, a);
-  const f32x2 e = {t[0] > 0.927734375f ? big[0] : small[0], t[1] > 0.927734375f ? big[1] : small[1]};
-  return 0.5f * v * (1.0f + e);
+  const f32x2 t = __builtin_elementwise_min(__builtin_elementwise_abs(v), (f32x2)8.48528137423857f);
+  f32x2 p = __builtin_elementwise_fma((f32x2)1.137868688e-09f, t, (f32x2)-5.171069262e-08f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)1.014483701e-06f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)-1.117507963e-05f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)7.388171798e-05f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)-2.645340865e-04f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)-3.723767077e-05f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)6.994847674e-03f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)-5.247364566e-02f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)-4.592104554e-01f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)-1.151105404e+00f);
+  p = __builtin_elementwise_fma(p, t, (f32x2)1.941864447e-08f);
+  const f32x2 E = {OMNI_EXP2(p[0]), OMNI_EXP2(p[1])};
+  const f32x2 c1 = __builtin_elementwise_copysign((f32x2)0.5f, v);
+  return v * __builtin_elementwise_fma(-c1, E, 0.5f + c1);
 }
 
 // per-kind launchers (each lives in its own .hip file)
