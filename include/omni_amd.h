@@ -87,6 +87,11 @@ enum {
    *           value = hi + lo (4 bytes per element, same strides as f32) — x written that way by its producer
    *           (OMNI_OP_LAYERNORM i6, this op's i21, OMNI_OP_SPLIT_CONVERT), w = split(W * 2^k) with f1 = 2^-k;
    *           i21 = 1: write y in format B as well (bias + activation applied first; no residual)
+   *           i26 = n > 0 (additive; 0 = one weight matrix): PER-IMAGE WEIGHTS.  Rows [b n, (b + 1) n) of x are image b (M % n == 0) and
+   *           multiply weight matrix b: p1 + b * i27 bytes (i27 % 16 == 0, i27 >= Cout * K * 4, or 0 = every image reads p1), each a
+   *           format-B matrix of its own with its own power of two: p6 = f32[M / n] of 2^-k, read in place of f1 (NULL = f1 for all).
+   *           n must be a multiple of the row tile the launcher takes (256, or 128 for short token matrices / OMNI_GEMM_TILE=128x128),
+   *           else OMNI_E_ARG: the image of a tile is then uniform.  Written by OMNI_OP_CHAN_ATTN's fold mode (i8 = 1)
    *  i22 / i23 (i20 = 1 only; 0 = the launcher's heuristic): output tile (1 = 64x64, 2 = 128x64, 3 = 128x128) and split-K count
    *           (1 = no split, no reduce launch) — the per-shape choices of a tuning table; the sums differ only in the order of the K partials
    *  i24 = n > 0 (i20 = 1 only; round 6): p6 = int32[n] ARRIVAL COUNTERS, all zero before the first launch that uses them.  A split-K
@@ -158,7 +163,14 @@ enum {
    *  queries: they are computed over the valid keys, stay finite, and nobody reads them as keys. */
   OMNI_OP_ATTN_ROWS = 10,
   /* DaViT grouped channel attention (florence2 :223-259): p0 qkv [B*N,3C] p4 o [B*N,C] p5 ws f32[B*G*chunks*1024]
-   *  i0 B i1 N i3 C i4 G i5 chunk_tokens i6 = 1: o in format B (f32 plans); f0 scale (0 => N^-0.5) */
+   *  i0 B i1 N i3 C i4 G i5 chunk_tokens i6 = 1: o in format B (f32 plans); f0 scale (0 => N^-0.5)
+   *  i8 = 1 (additive; f32 plans, C % 64 == 0, i5 % 8 == 0): FOLD MODE.  The group's 32x32 matrix A_g = softmax(scale q^T k) does not
+   *  depend on the token and the projection Wp behind the attention is linear, so proj(attn)[n][o] = sum_c W'_b[o][c] v[n][c] + bias with
+   *  W'_b[o][g32+j] = sum_i Wp[o][g32+i] A_g[i][j].  The op computes scores and softmax as always, then W'_b per image instead of the
+   *  apply pass: p1 Wp f32[C, C] (plain), p2 W' f32[B, C, C] (one fma chain per element, i ascending), p3 the same as format-B
+   *  matrices [B][C][C] of 4 bytes per element with W' 2^k = hi + lo, k per image such that the largest |W' 2^k| lies in [2^12, 2^13)
+   *  (clamped to +-24; 0 for a zero matrix), p6 f32[B] = 2^-k, p7 f32[B * (C / 64) * G] scratch (block maxima).  p4 is not written and
+   *  may be NULL; q and k are read from p0 as f32, v is not read.  p3 / p6 feed OMNI_OP_CONV i26 / i27 / p6 */
   OMNI_OP_CHAN_ATTN = 11,
   /* projector input (florence2 :568-590): y[b] = [mean_n(x+pos+t) ; x+pos+t]; p0 x [B,N,C] p1 pos2d f32[N,C] p2 temporal f32[C] p4 y [B,N+1,C]
    *  i0 B i1 N i3 C */

@@ -111,6 +111,18 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       ext[4] = span(M, i[13], i[14], Cout);
       ext[5] = i[19] > 0 ? (long long)i[19] * 1024 : 1;
       if (i[24] > 0) ext[6] = (long long)i[24] * 4;          // split-K arrival counters (in-launch combine); p6 is ignored when i24 == 0
+      if (i[20] == 2 && i[26] > 0) {                         // per-image weights: B weight matrices i27 bytes apart, p6 = their 2^-k
+        const long long nimg = (M + i[26] - 1) / i[26];
+        ext[1] += (nimg - 1) * (long long)i[27];
+        ext[6] = nimg * 4;
+      }
+      break;
+    }
+    case OMNI_OP_CHAN_ATTN: {
+      // p0 qkv [B*N,3C] p4 o [B*N,C] p5 ws; fold mode (i8 = 1): p1 Wp f32[C,C] p2 W' f32[B,C,C] p3 W' format B p6 2^-k f32[B] p7 block maxima
+      const long long B = i[0], N = i[1], C = i[3], G = i[4], ct = i[5] > 0 ? i[5] : 1;
+      ext[0] = B * N * 3 * C * esz; ext[4] = B * N * C * esz; ext[5] = B * G * ((N + ct - 1) / ct) * 1024 * 4;
+      if (i[8] == 1) { ext[1] = C * C * 4; ext[2] = ext[3] = B * C * C * 4; ext[6] = B * 4; ext[7] = B * (C / 64) * G * 4; }
       break;
     }
     case OMNI_OP_BEAM_STEP: {

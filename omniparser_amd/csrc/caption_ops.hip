@@ -1662,6 +1662,98 @@ __global__ __launch_bounds__(256, 2) void chan_apply_mfma_split_kernel(ChanArgs 
 }
 
 
+// ---- fold mode of OMNI_OP_CHAN_ATTN (i8 = 1): the apply pass is not run.  The (image, group)'s 32x32 matrix A_g is constant over the
+// image's tokens and the projection behind the attention is linear, so
+//   y[n][o] = sum_c Wp[o][c] out[n][c] + bp[o] = sum_{g,j} ( sum_i Wp[o][g32+i] A_g[i][j] ) v[n][g32+j] + bp[o] = sum_c W'_b[o][c] v[n][c] + bp[o]
+// and the projection GEMM reads v with a weight matrix of its own per image (gemm_dma.hip: GemmArgs::img_tiles) — no attention output
+// tensor, no pass over the tokens.  Two small kernels behind chan_softmax_kernel:
+//   chan_fold_kernel       W'_b = Wp . blockdiag(A_g) in f32, one fma chain per output (i ascending), 64 output rows x one group per
+//                          block; max |W'| of the block goes to a per-block slot (no atomics, nothing to zero between replays)
+//   chan_fold_pack_kernel  max over the image's blocks -> k as planner.split_f16_b chooses it (largest |W' 2^k| in [2^12, 2^13), clamped
+//                          to +-24, 0 for a zero matrix), 2^-k to the scale table, W' 2^k as format B (hi = f16(x), lo = f16(x - hi),
+//                          both round-to-nearest like the host packing of the shared weights)
+struct FoldArgs {
+  const float* ws; const float* wp; float* wf; float* bmax; unsigned char* wb; float* osc;
+  int C, G, chunks, nblk;
+};
+
+__global__ __launch_bounds__(256) void chan_fold_kernel(FoldArgs a) {
+  __shared__ float sA[32][32];
+  __shared__ float sW[64][33];
+  __shared__ float smax[4];
+  const int ob = blockIdx.x, g = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const float* A = a.ws + ((long long)b * a.G + g) * a.chunks * 1024;
+  for (int e = tid; e < 1024; e += 256) sA[e >> 5][e & 31] = A[e];
+  for (int e = tid; e < 64 * 32; e += 256) sW[e >> 5][e & 31] = a.wp[(long long)(ob * 64 + (e >> 5)) * a.C + g * 32 + (e & 31)];
+  __syncthreads();
+  const int r = tid >> 2, j0 = (tid & 3) * 8;
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+#pragma unroll 8
+  for (int i = 0; i < 32; ++i) {
+    const float w = sW[r][i];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = fmaf(w, sA[i][j0 + e], acc[e]);
+  }
+  float* out = a.wf + ((long long)b * a.C + ob * 64 + r) * a.C + g * 32 + j0;
+  *reinterpret_cast<f32x4*>(out) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+  *reinterpret_cast<f32x4*>(out + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+  float m = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(acc[e]));
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((tid & 63) == 0) smax[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) a.bmax[(long long)b * a.nblk + ob * a.G + g] = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
+}
+
+__global__ __launch_bounds__(256) void chan_fold_pack_kernel(FoldArgs a) {
+  __shared__ float red[256];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  float m = 0.0f;
+  for (int e = tid; e < a.nblk; e += 256) m = fmaxf(m, a.bmax[(long long)b * a.nblk + e]);
+  red[tid] = m;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
+    __syncthreads();
+  }
+  const float amax = red[0];
+  int k = 0;
+  if (amax > 0.0f) {                                           // 12 - floor(log2(amax)): the exponent field (a subnormal maximum clamps anyway)
+    k = 12 - ((int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu) - 127);
+    k = max(-24, min(24, k));
+  }
+  const float up = __builtin_bit_cast(float, (unsigned)(127 + k) << 23);
+  if (blockIdx.x == 0 && tid == 0) a.osc[b] = __builtin_bit_cast(float, (unsigned)(127 - k) << 23);
+  const int gpr = a.C / 16;
+  const int idx = blockIdx.x * 256 + tid;
+  if (idx >= a.C * gpr) return;
+  const float* src = a.wf + (long long)b * a.C * a.C + (long long)idx * 16;
+  half_t h[32];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * q) * up;      // exact: a power of two, |v| < 2^13
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const half_t hi = (half_t)v[e];
+      h[4 * q + e] = hi;
+      h[16 + 4 * q + e] = (half_t)(v[e] - (float)hi);
+    }
+  }
+  unsigned char* dst = a.wb + ((long long)b * a.C * a.C + (long long)idx * 16) * 4;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    f16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = h[8 * q + e];
+    *reinterpret_cast<f16x8*>(dst + 16 * q) = o;
+  }
+}
+
+
 // ------------------------------------------------------------------------------------ small glue kernels
 struct PrepArgs { const void* x; const float* pos; const float* temporal; void* y; int B, N, C; };
 
@@ -2698,7 +2790,11 @@ static int launch_chan_attn(const omni_op_t* op, hipStream_t s) {
   ChanArgs a{};
   a.qkv = op->p[0]; a.o = op->p[4]; a.ws = (float*)op->p[5];
   a.B = op->i[0]; a.N = op->i[1]; a.C = op->i[3]; a.G = op->i[4]; a.chunk_tokens = op->i[5]; a.osplit = op->i[6];
-  OMNI_REQUIRE(a.qkv && a.o && a.ws && a.B > 0 && a.N > 0 && a.C == a.G * 32 && a.chunk_tokens > 0, "chan_attn: bad arguments");
+  const bool fold = op->i[8] == 1;         // fold mode: scores + softmax + W'_b = Wp . blockdiag(A) per image, no apply pass (p4 unused)
+  OMNI_REQUIRE(a.qkv && (a.o || fold) && a.ws && a.B > 0 && a.N > 0 && a.C == a.G * 32 && a.chunk_tokens > 0, "chan_attn: bad arguments");
+  OMNI_REQUIRE(op->i[8] == 0 || fold, "chan_attn: unknown mode %d", op->i[8]);
+  OMNI_REQUIRE(!fold || (op->dtype == OMNI_F32 && a.chunk_tokens % 8 == 0 && a.C % 64 == 0 && op->p[1] && op->p[2] && op->p[3] && op->p[6] && op->p[7]),
+               "chan_attn: fold mode needs an f32 plan, C %% 64 == 0, chunk_tokens %% 8 == 0 and p1 / p2 / p3 / p6 / p7");
   OMNI_REQUIRE(!a.osplit || op->dtype == OMNI_F32, "chan_attn: split output needs an f32 plan");
   a.chunks = (a.N + a.chunk_tokens - 1) / a.chunk_tokens;
   a.scale = 1.0f / sqrtf((float)a.N);
@@ -2707,6 +2803,16 @@ static int launch_chan_attn(const omni_op_t* op, hipStream_t s) {
   if (op->dtype == OMNI_F32 && a.chunk_tokens % 8 == 0 && a.C % 4 == 0) {
     hipLaunchKernelGGL(chan_scores_mfma_kernel, g1, dim3(256), 0, s, a);
     hipLaunchKernelGGL(chan_softmax_kernel, dim3(a.G, a.B), dim3(256), 0, s, a);
+    if (fold) {
+      FoldArgs f{};
+      f.ws = a.ws; f.wp = (const float*)op->p[1]; f.wf = (float*)op->p[2]; f.wb = (unsigned char*)op->p[3]; f.osc = (float*)op->p[6];
+      f.bmax = (float*)op->p[7];
+      f.C = a.C; f.G = a.G; f.chunks = a.chunks; f.nblk = (a.C / 64) * a.G;
+      hipLaunchKernelGGL(chan_fold_kernel, dim3(a.C / 64, a.G, a.B), dim3(256), 0, s, f);
+      hipLaunchKernelGGL(chan_fold_pack_kernel, dim3((a.C * (a.C / 16) + 255) / 256, a.B), dim3(256), 0, s, f);
+      OMNI_HIP_CHECK(hipGetLastError());
+      return OMNI_OK;
+    }
     hipLaunchKernelGGL(chan_apply_mfma_split_kernel, g2, dim3(256), 0, s, a);
     OMNI_HIP_CHECK(hipGetLastError());
     return OMNI_OK;

@@ -38,6 +38,10 @@ struct GemmArgs {
   int ldi, in_coff, ldo, out_coff, ldr, res_coff;
   int mtiles, ntiles, xcd_order, xcd_n;
   float oscale;                       // 2^-k of the weight pre-scale
+  // per-image weights (channel attention folded into its projection, caption_ops.hip::chan_fold_*): the rows of tile-row mt belong to
+  // image mt / img_tiles, whose weight matrix lies img * w_img_stride bytes behind w and whose 2^-k is img_oscale[img].
+  // img_tiles == 0: one weight matrix and `oscale` for all rows
+  int img_tiles; unsigned w_img_stride; const float* img_oscale;
 };
 
 // 16-byte row accesses of an epilogue through a buffer descriptor that ends with the last valid row of the tile: the hardware's range
@@ -71,7 +75,7 @@ struct RowBuf {
 // that end with the wave's last channel of row min(M, m0 + BM) - 1.  2^-k is a power of two, so acc * 2^-k is exact and ONE fma
 // gives the bits of multiply + add (outside the subnormal range).
 template <int BM, int BN, int WM, int WN, int TM, int TN, int LDS_BYTES, int ACT, bool OSPLIT, bool RES>
-__device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& a, unsigned char* lds, int m0, int n0, int wave, int lane) {
+__device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& a, unsigned char* lds, int m0, int n0, int wave, int lane, float osc) {
   constexpr int NW = WM * WN;
   const int wm = wave / WN, wn = wave % WN;
   const int hsel = lane >> 5;
@@ -80,7 +84,6 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
   static_assert(NW * 32 * EP <= LDS_BYTES, "epilogue staging must fit the LDS ring");
   __syncthreads();                                           // every wave is done reading the last K slice
   unsigned char* stg = lds + wave * (32 * EP);
-  const float osc = a.oscale;
   float amax = 0.0f;                                         // range guard of the split output (omni_internal.h)
   const int rrow = lane >> 4, chunk = lane & 15;             // read phase: 16 lanes per row, 16 bytes per lane
   const int trows = min(a.M - m0, BM), wc0 = n0 + wn * (BN / WN);   // valid rows of the tile (>= 1), first channel of this wave
@@ -191,6 +194,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_dma_kernel(GemmArgs a) {
   // block-uniform by construction; said explicitly so that the buffer resources below are built in SGPRs (the division inside
   // tile_of_block runs on the VALU, and a resource the compiler believes divergent costs a waterfall loop per LDS-DMA instruction)
   const int m0 = __builtin_amdgcn_readfirstlane(mt) * BM, n0 = __builtin_amdgcn_readfirstlane(nt) * BN;
+  // per-image weights: the launcher made an image a whole number of tile rows, so the image of a tile is block-uniform too — kept in
+  // an SGPR for the same reason (it goes into the weight resource); its 2^-k is a scalar load that lands long before the epilogue
+  const int img = a.img_tiles ? __builtin_amdgcn_readfirstlane(mt / a.img_tiles) : 0;
+  const float osc = a.img_oscale ? a.img_oscale[img] : a.oscale;
 
   // ---- LDS-DMA descriptors.  Piece p (8 rows x 128 B) of an operand tile lands at LDS piece slot p; lane l of the
   // issuing wave supplies row 8p + l/8, 16-byte slot l%8, whose SOURCE chunk is slot ^ ((row >> 1) & 7).
@@ -215,7 +222,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_dma_kernel(GemmArgs a) {
   const __amdgpu_buffer_rsrc_t rsrcA =
       __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + ((long long)m0 * a.ldi + a.in_coff) * 4), 0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcB =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(a.w + (long long)n0 * a.K * 4), 0, 0x7fffffff, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)(a.w + (long long)img * a.w_img_stride + (long long)n0 * a.K * 4), 0, 0x7fffffff, 0x00020000);
   // piece i of slice kt into ring slot `stage` (i < A_DMA: activation rows, else weight rows)
   auto issue_piece = [&](int kt, int stage, int i) {
     const int so = kt * 128;
@@ -408,7 +415,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_dma_kernel(GemmArgs a) {
   }
 
   // ---- epilogue (gemm_epilogue above): bias / activation / 2^-k in registers, rows transposed through the idle LDS ring
-  gemm_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE, ACT, OSPLIT, RES>(acc, a, lds, m0, n0, wave, lane);
+  gemm_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE, ACT, OSPLIT, RES>(acc, a, lds, m0, n0, wave, lane, osc);
 #endif
 }
 
@@ -593,12 +600,17 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_kernel(MlpArgs a) {
   }
   omni_report_range(amax);
   // ---- epilogue: 2^-k2, fc2 bias, residual, coalesced f32 rows (gemm_epilogue: four waves x 32 tokens x 128 channels)
-  gemm_epilogue<NW * 32, C, NW, 1, 1, OB, 2 * STAGE, OMNI_ACT_NONE, false, true>(acc2, a.ep, lds, m0, 0, wave, lane);
+  gemm_epilogue<NW * 32, C, NW, 1, 1, OB, 2 * STAGE, OMNI_ACT_NONE, false, true>(acc2, a.ep, lds, m0, 0, wave, lane, a.ep.oscale);
 #endif
 }
 
 template <int BM, int BN, int WM, int WN, int NSTAGE>
-int launch_tile(GemmArgs& a, int act, int osplit, hipStream_t s) {
+int launch_tile(GemmArgs& a, int rows_per_img, int act, int osplit, hipStream_t s) {
+  if (rows_per_img % BM != 0) {
+    omni_set_error("gemm_dma: per-image weights need whole %d-row tiles per image (rows per image %d)", BM, rows_per_img);
+    return OMNI_E_ARG;
+  }
+  a.img_tiles = rows_per_img / BM;
   a.mtiles = (a.M + BM - 1) / BM;
   a.ntiles = a.N / BN;
   a.xcd_order = (a.mtiles >= 64 && a.ntiles > 1) ? 1 : 0;
@@ -662,6 +674,15 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE((long long)a.ldi * 4 * 256 < (1ll << 31) && (long long)a.K * 4 * 256 < (1ll << 31) && (long long)a.ldo * 4 * 256 < (1ll << 31) &&
                (long long)a.ldr * 4 * 256 < (1ll << 31), "gemm_dma: row stride too large");
   a.nk = a.K / 32;
+  // per-image weights (i26 rows per image, i27 bytes between the images' matrices, p6 their 2^-k): see GemmArgs
+  const int rows_per_img = op->i[26];
+  OMNI_REQUIRE(rows_per_img >= 0 && op->i[27] >= 0, "gemm_dma: bad per-image weight arguments (%d rows, stride %d)", rows_per_img, op->i[27]);
+  if (rows_per_img > 0) {
+    OMNI_REQUIRE(a.M % rows_per_img == 0, "gemm_dma: %d rows are no whole number of images of %d rows", a.M, rows_per_img);
+    OMNI_REQUIRE(op->i[27] % 16 == 0 && (op->i[27] == 0 || op->i[27] >= a.N * a.K * 4), "gemm_dma: per-image weight stride %d (N %d, K %d)", op->i[27], a.N, a.K);
+    a.w_img_stride = (unsigned)op->i[27];
+    a.img_oscale = (const float*)op->p[6];
+  }
   // tile choice: 256x256 (one 8-wave block per CU, 128x64 per wave) when N allows, 256x128 otherwise — as long as the launch
   // still has a block for every CU; a short token matrix (small caption batches, 64x64 crops) takes 128x128 tiles instead, which
   // quarter the padded rows and give the chip 4x the blocks.  OMNI_GEMM_TILE (256x256 | 256x128 | 128x128) is the A/B knob of
@@ -677,9 +698,9 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
     else if (!strcmp(e, "256x256") && a.N % 256 == 0) tile = 0;
   }
   int rc;
-  if (tile == 0) rc = launch_tile<256, 256, 2, 4, 2>(a, act, osplit, s);
-  else if (tile == 1) rc = launch_tile<256, 128, 4, 2, 3>(a, act, osplit, s);
-  else rc = launch_tile<128, 128, 2, 2, 2>(a, act, osplit, s);
+  if (tile == 0) rc = launch_tile<256, 256, 2, 4, 2>(a, rows_per_img, act, osplit, s);
+  else if (tile == 1) rc = launch_tile<256, 128, 4, 2, 3>(a, rows_per_img, act, osplit, s);
+  else rc = launch_tile<128, 128, 2, 2, 2>(a, rows_per_img, act, osplit, s);
   if (rc) return rc;
   OMNI_HIP_CHECK(hipGetLastError());
   return OMNI_OK;

@@ -720,6 +720,7 @@ class _CaptionPlans(_StepPlans):
         x = self.x_in
         vt = "model.vision_tower."
         self.chan_ws = None
+        self.fold_stages = []        # DaViT stages whose channel blocks run folded (Florence2Captioner.fold_chan_proj)
         self.stage_out = []          # output of every DaViT stage (valid after the encode plan unless cap.reuse_activations: each stage owns its buffers)
         for s in range(4):
             C = w.embed_dim[s]
@@ -762,6 +763,17 @@ class _CaptionPlans(_StepPlans):
             chunk_tokens = 1024
             chunks = (N + chunk_tokens - 1) // chunk_tokens
             cws = pb.raw((B * w.groups[s] * chunks * 1024,), torch.float32, zero=False)
+            # fold rule: the fold's bytes and MACs grow with C^2 per image, what it saves with N * C — worth it from N >= 4 C on;
+            # whole 256-row GEMM tiles per image.  768x768 crops: stages 0-2; 64x64 crops: none
+            fold = bool(cap.fold_chan_proj) and grp["dma"] and dt == L.F32 and C % 128 == 0 and N % 256 == 0 and N >= 4 * C
+            fold_wf = fold_wb = fold_sc = fold_mx = None
+            if fold:                                      # stage scratch, image-major: an exact-row twin uses the first n images' part
+                fold_wf = pb.raw((B * C * C,), torch.float32, zero=False)
+                fold_wb = pb.raw((B * C * C,), torch.float32, zero=False)
+                fold_sc = pb.raw((B,), torch.float32, zero=False)
+                fold_mx = pb.raw((B * (C // 64) * w.groups[s],), torch.float32, zero=False)
+            if fold:
+                self.fold_stages.append(s)
             for blk in range(w.depths[s]):
                 for kind in ("spatial_block", "channel_block"):
                     pre = f"{vt}blocks.{s}.{blk}.{kind}."
@@ -778,6 +790,27 @@ class _CaptionPlans(_StepPlans):
                             f={0: (C // w.heads[s]) ** -0.5}))
                         att.fmt = "split" if (attn_split and grp["dma"]) else "f32"
                         linear(pre + "window_attn.proj", att, B_, res=B_)
+                    elif fold:
+                        # channel attention folded into its projection (csrc/caption_ops.hip "fold mode"): q|k in f32 for the scores,
+                        # v straight into format B (two launches over row slices of the ONE packed q|k|v weight), softmax + fold write
+                        # this block's per-image projection weights, and the projection reads v through them — no apply pass, no `att`
+                        key = pre + "channel_attn.qkv"
+                        wp, _ = W.linear([key], dma=True)
+                        wqk, bqk, wv, bv = W.cached((key, dt, "dma-qk|v"), lambda: (
+                            pb.weight_rows(wp, 0, 2 * C), pb.upload(sd[key + ".bias"][:2 * C].float()),
+                            pb.weight_rows(wp, 2 * C, C), pb.upload(sd[key + ".bias"][2 * C:].float())))
+                        assert hbuf.fmt == "split"
+                        pb.conv(tokens(hbuf), wqk, bqk, tokens(qkv.slice(0, 2 * C)), 1)
+                        vs = tokens(qkv.slice(2 * C, C))
+                        pb.conv(tokens(hbuf), wv, bv, vs, 1, out_split=True)
+                        pkey = pre + "channel_attn.proj"
+                        wplain, bproj = W.f32(pkey + ".weight"), W.f32(pkey + ".bias")
+                        pb.keep += [wplain, bproj]
+                        pb.add_op(L.make_op(L.OP_CHAN_ATTN, dt,
+                                            p=[qkv.ptr, wplain.data_ptr(), fold_wf.data_ptr(), fold_wb.data_ptr(), None, cws.data_ptr(),
+                                               fold_sc.data_ptr(), fold_mx.data_ptr()],
+                                            i={0: B, 1: N, 3: C, 4: w.groups[s], 5: chunk_tokens, 6: 1 if (attn_split and grp["dma"]) else 0, 8: 1}))
+                        pb.conv_per_image(vs, fold_wb, fold_sc, bproj, tokens(B_), tokens(B_), N)
                     else:
                         linear(pre + "channel_attn.qkv", hbuf, qkv)
                         pb.add_op(L.make_op(L.OP_CHAN_ATTN, dt, p=[qkv.ptr, None, None, None, att.ptr, cws.data_ptr()],
@@ -797,7 +830,7 @@ class _CaptionPlans(_StepPlans):
             x = A_
             self.stage_out.append(A_)
             # reuse_activations: the stage's scratch tensors back the (smaller) tensors of the next stages
-            pb.release(B_, hbuf, qkv, att, ffn, cws)
+            pb.release(B_, hbuf, qkv, att, ffn, cws, fold_wf, fold_wb, fold_sc, fold_mx)
         self.vision_out = x
         grp["dma"] = use_dma
         # ---------------- projector
@@ -943,6 +976,8 @@ class Florence2Captioner:
     # plan composition switches (class attributes: the tests build the round-2 composition by overriding them)
     fuse_dwln = True          # x + dwconv(x) -> LayerNorm as one strip kernel (DaViT stages 0-2)
     attn_split_out = True     # attention kernels write format B for the projection GEMM themselves
+    fold_chan_proj = True     # channel attention's apply pass folded into a per-image projection weight where N >= 4 C (f32 LDS-DMA plans;
+                              # DaViT stages 0-2 at 768x768, nothing at 64x64): OMNI_OP_CHAN_ATTN i8 = 1 + OMNI_OP_CONV i26 / i27 / p6
     fuse_mlp = True           # fc1 + GELU + fc2 + residual of the C = 128 stage as ONE kernel (OMNI_OP_MLP_FUSED): no hidden tensor in HBM
     exact_rows = os.environ.get("OMNI_EXACT_ROWS", "1") != "0"   # merged decode: the remainder micro-batch of a caption batch encodes exactly
                               # its own rows, as a second hipGraph over the buffers of the lane's full-capacity plan (`_CaptionPlans.encode_rows`),

@@ -327,6 +327,42 @@ class PlanBuilder:
         self.bytes += esz * (x.B * x.H * x.W * x.C + w_packed.numel() // (2 if wfmt else 1) + M * cout * (2 if res is not None else 1))
         return out
 
+    @staticmethod
+    def weight_rows(w_packed: torch.Tensor, row0: int, rows: int) -> torch.Tensor:
+        """output rows [row0, row0 + rows) of a format-B weight as a weight of its own (a view: same bytes, same 2^-k) — one packed
+        q|k|v matrix serves launches over parts of its output channels"""
+        assert getattr(w_packed, "omni_fmt", 0) == 2 and 0 <= row0 and row0 + rows <= w_packed.shape[0]
+        t = w_packed[row0:row0 + rows]
+        t.omni_fmt, t.omni_oscale = 2, w_packed.omni_oscale
+        return t
+
+    def conv_per_image(self, x: View, w_img: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor], out: View,
+                       res: Optional[View], rows_per_img: int):
+        """pointwise layer on the LDS-DMA GEMM whose weight matrix differs per image (OMNI_OP_CONV i20 = 2 with i26 / i27 / p6):
+        image b = rows [b * rows_per_img, (b + 1) * rows_per_img) of x multiplies the format-B matrix b of `w_img` ([images, Cout * Cin]
+        4-byte elements, written on the device by OMNI_OP_CHAN_ATTN's fold mode) and scales[b] = its 2^-k."""
+        cout, K = out.C, x.C
+        M = x.B * x.H * x.W
+        assert self.dtype == L.F32 and x.fmt == "split" and x.ld % 16 == 0 and x.coff % 16 == 0 and cout % 128 == 0 and K % 32 == 0
+        assert (out.B, out.H, out.W) == (x.B, x.H, x.W) and M % rows_per_img == 0
+        nimg = M // rows_per_img
+        assert w_img.numel() * w_img.element_size() >= nimg * cout * K * 4 and scales.dtype == torch.float32 and scales.numel() >= nimg
+        assert bias is None or (bias.dtype == torch.float32 and bias.numel() == cout and bias.device.type == self.device.type)
+        if res is not None:
+            assert (res.B, res.H, res.W, res.C) == (out.B, out.H, out.W, out.C) and res.fmt == "f32"
+        self.ops.append(L.make_op(
+            L.OP_CONV, self.dtype,
+            p=[x.ptr, w_img.data_ptr(), bias.data_ptr() if bias is not None else None, res.ptr if res is not None else None, out.ptr,
+               None, scales.data_ptr()],
+            i={0: x.B, 1: x.H, 2: x.W, 3: K, 4: x.ld, 5: x.coff, 6: 1, 7: 1, 8: 1, 9: 0, 10: x.H, 11: x.W, 12: cout, 13: out.ld, 14: out.coff,
+               15: L.ACT_NONE, 16: res.ld if res is not None else 0, 17: res.coff if res is not None else 0, 20: 2,
+               26: rows_per_img, 27: cout * K * 4}))
+        self.keep += [w_img, scales] + ([bias] if bias is not None else [])
+        out.fmt = "f32"
+        self.flops += 2 * M * cout * K                     # the projection's algorithmic work: unchanged by where its weights come from
+        self.bytes += 4 * (M * K + nimg * cout * K + M * cout * (2 if res is not None else 1))
+        return out
+
     def pack_weight_patch(self, w: torch.Tensor, ld: int = 4) -> torch.Tensor:
         """[Cout, Cin <= ld, k, k] f32 (k <= 8) -> split-f16 weight of the ROW-PATCH form of the convolution (conv_patch):
         [Cout][k rows][8 pixels][ld channels], zero beyond tap k - 1 and beyond channel Cin - 1."""
