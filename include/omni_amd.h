@@ -92,8 +92,10 @@ enum {
    *           format-B matrix of its own with its own power of two: p6 = f32[M / n] of 2^-k, read in place of f1 (NULL = f1 for all).
    *           n must be a multiple of the row tile the launcher takes (256, or 128 for short token matrices / OMNI_GEMM_TILE=128x128),
    *           else OMNI_E_ARG: the image of a tile is then uniform.  Written by OMNI_OP_CHAN_ATTN's fold mode (i8 = 1)
-   *  i22 / i23 (i20 = 1 only; 0 = the launcher's heuristic): output tile (1 = 64x64, 2 = 128x64, 3 = 128x128) and split-K count
-   *           (1 = no split, no reduce launch) — the per-shape choices of a tuning table; the sums differ only in the order of the K partials
+   *  i22 (i20 = 0 or 1; 0 = the launcher's heuristic): output tile (1 = 64x64, 2 = 128x64, 3 = 128x128).  With i20 = 0 the K-slice
+   *           width and the split-K count still follow from the tile as they do unforced (128-row tiles walk 64-byte slices)
+   *  i23 (i20 = 1 only, ignored otherwise; 0 = the heuristic): split-K count (1 = no split, no reduce launch).  i22 / i23 are the
+   *           per-shape choices of a tuning table; the sums differ only in the order of the K partials
    *  i24 = n > 0 (i20 = 1 only; round 6): p6 = int32[n] ARRIVAL COUNTERS, all zero before the first launch that uses them.  A split-K
    *           launch with at most n output tiles then combines its partials INSIDE the conv launch (each split publishes its tile
    *           write-through and draws a ticket; the last arriver sums in split order, applies bias / act / residual and zeroes the
@@ -368,6 +370,15 @@ int omni_plan_profile(omni_plan_t* plan, void* stream, float* h_ms);
  * weight_bytes < 0: use `xcd_n` (1, 2, 4 or 8, must divide ntiles). */
 int omni_debug_tile_map(int mtiles, int ntiles, int xcd_n, long long weight_bytes, int bid, int* mt, int* nt, int* grid,
                         int* xcd_n_used);
+
+/* What omni_op_launch would launch for an OMNI_OP_CONV op with i20 = 0 or 1, computed by the function the launcher itself calls.
+ * Test/diagnostic entry point, no device work, no pointer of the op is dereferenced (p0, p1, p4 must be non-NULL; p5 / p6 count
+ * as "workspace / counters present").  The op's own argument errors are returned as they would be by the launch.
+ *   out[0] kernel family: 0 = register-staged f32 MFMA, 1 = register-staged f16 MFMA, 2 = split-f16 (i20 = 1)
+ *   out[1] BM  out[2] BN  (output tile)   out[3] RB (bytes of K per slice row)
+ *   out[4] loader: 0 = generic (ragged K vectors), 1 = aligned, 2 = pointwise, 3 = row-patch (i25)
+ *   out[5] split-K count   out[6] 0 = no split-K, 1 = reduce launch, 2 = in-launch combine (i24)   out[7] waves per workgroup */
+int omni_debug_conv_cfg(const omni_op_t* op, int out[8]);
 
 /* ------------------------------------------------------------------------ *
  * Model-level entry points: the two models of the hot path for hosts

@@ -27,6 +27,7 @@ EXPORTS = [
     "omni_last_error", "omni_abi_version", "omni_device_count", "omni_op_launch",
     "omni_plan_create", "omni_plan_run", "omni_plan_capture", "omni_plan_replay",
     "omni_plan_num_ops", "omni_plan_destroy", "omni_resample_coeffs", "omni_plan_time", "omni_debug_tile_map",
+    "omni_debug_conv_cfg",
     "omni_plan_profile",
     "omni_model_load", "omni_model_destroy", "omni_model_int", "omni_model_tensor", "omni_model_run",
     "omni_detector_create", "omni_detector_infer", "omni_captioner_create", "omni_captioner_caption",
@@ -96,6 +97,8 @@ def bind(path):
     L.omni_debug_tile_map.argtypes = [c_int, c_int, c_int, ctypes.c_longlong, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                       POINTER(c_int)]
     L.omni_debug_tile_map.restype = c_int
+    L.omni_debug_conv_cfg.argtypes = [POINTER(OmniOp), POINTER(c_int)]
+    L.omni_debug_conv_cfg.restype = c_int
     c_ll = ctypes.c_longlong
     for name in ("omni_model_load", "omni_detector_create", "omni_captioner_create"):
         fn = getattr(L, name)
@@ -294,6 +297,19 @@ def tile_map(mtiles: int, ntiles: int, bid: int, xcd_n: int = 1, weight_bytes: i
     check(lib().omni_debug_tile_map(mtiles, ntiles, xcd_n, weight_bytes, bid, ctypes.byref(mt), ctypes.byref(nt), ctypes.byref(grid),
                                     ctypes.byref(used)))
     return mt.value, nt.value, grid.value, used.value
+
+
+CONV_FAMILIES = ("f32", "f16", "split")
+CONV_LOADERS = ("generic", "aligned", "pointwise", "row_patch")
+CONV_REDUCE = ("none", "reduce_launch", "in_launch_combine")
+
+
+def conv_cfg(op: OmniOp) -> dict:
+    """What omni_op_launch would launch for a conv op (omni_debug_conv_cfg: the launcher's own choice; no device work)."""
+    out = (c_int * 8)()
+    check(lib().omni_debug_conv_cfg(ctypes.byref(op), out))
+    return {"family": CONV_FAMILIES[out[0]], "bm": out[1], "bn": out[2], "rb": out[3], "loader": CONV_LOADERS[out[4]],
+            "splits": out[5], "reduce": CONV_REDUCE[out[6]], "waves": out[7]}
 
 
 class CModel:

@@ -634,16 +634,22 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_split_kernel(ConvArgs a) {
   else run(std::integral_constant<int, OMNI_ACT_NONE>{});
 }
 
+// What omni_launch_conv launches for one op.  The choice is made ONCE, by plan_conv below: the launcher executes it and
+// omni_debug_conv_cfg reports it, so a test that asks which kernel a shape lands on reads the launcher's own decision.
+enum { CONV_FAMILY_F32 = 0, CONV_FAMILY_F16 = 1, CONV_FAMILY_SPLIT = 2 };       // conv_igemm_kernel<float> / <half_t>, conv_split_kernel
+enum { CONV_LOADER_GENERIC = 0, CONV_LOADER_ALIGNED = 1, CONV_LOADER_POINTWISE = 2, CONV_LOADER_ROW_PATCH = 3 };
+struct ConvPlan {
+  int family, bm, bn, rb, loader, waves;      // splits / kt_per_split / ktiles / cin_tiles / cnt live in ConvArgs (the kernels read them)
+};
+
 template <int BM, int BN>
-void launch_split_cfg(ConvArgs& a, hipStream_t s) {
+void launch_split_cfg(ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   a.mtiles = (a.M + BM - 1) / BM;
   a.ntiles = (a.Cout + BN - 1) / BN;
   a.xcd_order = (a.mtiles >= 64 && a.ntiles > 1) ? 1 : 0;
   a.xcd_n = a.xcd_order ? choose_xcd_n(a.ntiles, 4ll * a.Cout * a.K) : 1;      // 4 bytes per (n, k): hi | lo halves
   dim3 grid(tile_grid(a.mtiles, a.ntiles, a.xcd_order, a.xcd_n), 1, a.splits);
-  // row-patch mode (vec_px) never takes the PW loader: that one reads the 8 vectors of a slice as 8 channels of ONE pixel, unchecked,
-  // i.e. up to 7 pixels beyond the input for a 1 x 1 patch (0-weight taps x whatever lies there, NaN included)
-  const bool pw = !a.vec_px && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo;
+  const bool pw = p.loader == CONV_LOADER_POINTWISE;
   // 128x128: 8 waves (64x32 per wave, 4 waves/SIMD; measured 191-229 TF/s vs 172-209 for 4 waves of 64x64); smaller
   // tiles: 4 waves.  Round-1 variants that lost (two-slice register prefetch, weights straight to registers, 256x128,
   // 64-wide K slices, weight-only LDS-DMA) are recorded in DESIGN.md and profiles/r2_gemm_diag.md, not kept here.
@@ -665,7 +671,7 @@ void launch_split_cfg(ConvArgs& a, hipStream_t s) {
 // aims at >= 512-768 workgroups; for the latency-bound layers of a batch-1 detector pass (M = 400 ... 6 400: a kernel costs 5-13 us
 // whatever it computes, and every split-K conv is followed by a ~5.5 us reduce launch — 24 % of the pass in round 5's kernel trace)
 // fewer, longer blocks without the reduce are often faster.  Any choice gives the same sums up to the order of the K partials.
-int launch_split(ConvArgs& a, long long ws_bytes, hipStream_t s, int force_tile, int force_splits, int* cnt, int n_cnt) {
+int plan_split(ConvArgs& a, long long ws_bytes, int force_tile, int force_splits, int* cnt, int n_cnt, ConvPlan& p) {
   a.cin_tiles = a.Cin / 32;
   a.ktiles = a.K / 32;
   // 128x128 at 2 waves/SIMD is the fastest split tile (measured 171-207 TF/s vs 128-165 for 128x64); the
@@ -698,97 +704,91 @@ int launch_split(ConvArgs& a, long long ws_bytes, hipStream_t s, int force_tile,
   a.splits = (a.ktiles + a.kt_per_split - 1) / a.kt_per_split;
   // in-launch combine when the caller provided arrival counters for every output tile (else: the reduce launch)
   a.cnt = (a.splits > 1 && cnt && nb <= n_cnt) ? cnt : nullptr;
-  if (bm == 128 && bn == 128) launch_split_cfg<128, 128>(a, s);
-  else if (bm == 128 && bn == 64) launch_split_cfg<128, 64>(a, s);
-  else launch_split_cfg<64, 64>(a, s);
+  // row-patch mode (vec_px) never takes the PW loader: that one reads the 8 vectors of a slice as 8 channels of ONE pixel, unchecked,
+  // i.e. up to 7 pixels beyond the input for a 1 x 1 patch (0-weight taps x whatever lies there, NaN included)
+  const bool pw = !a.vec_px && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo;
+  p.family = CONV_FAMILY_SPLIT;
+  p.bm = bm; p.bn = bn; p.rb = 128;
+  p.loader = a.vec_px ? CONV_LOADER_ROW_PATCH : pw ? CONV_LOADER_POINTWISE : CONV_LOADER_ALIGNED;
+  p.waves = (bm == 128 && bn == 128) ? 8 : 4;
   return OMNI_OK;
 }
 
 template <typename T, int BM, int BN, int RB>
-void launch_cfg(ConvArgs& a, bool aligned, hipStream_t s) {
+int launch_cfg(ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   a.mtiles = (a.M + BM - 1) / BM;
   a.ntiles = (a.Cout + BN - 1) / BN;
   a.xcd_order = (a.mtiles >= 64 && a.ntiles > 1) ? 1 : 0;
   a.xcd_n = 1;                                  // exact-f32 / f16 kernels: row-block mapping only
   dim3 grid(tile_grid(a.mtiles, a.ntiles, a.xcd_order, a.xcd_n), 1, a.splits);
-  const bool pw = aligned && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo;
-  if (pw)
+  if (p.loader == CONV_LOADER_POINTWISE)
     hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, RB, true, true>), grid, dim3(256), 0, s, a);
-  else if (aligned)
+  else if (p.loader == CONV_LOADER_ALIGNED)
     hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, RB, true, false>), grid, dim3(256), 0, s, a);
-  else
+  else if constexpr (RB == 64)                  // a 128-byte slice is only chosen when Cin fills it: never with the generic loader
     hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, RB, false, false>), grid, dim3(256), 0, s, a);
+  else
+    OMNI_REQUIRE(false, "conv: no generic loader for %d-byte K slices", RB);
   if (a.splits > 1) {
     long long total = (long long)a.M * a.Cout;
     hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
   }
+  return OMNI_OK;
 }
 
-struct ConvCfg { int bm, bn, rb, splits, kt_per_split, ktiles, cin_tiles; bool aligned; };
-
-// Tile / split-K choice.  MI355X has 256 CUs x 4 SIMDs; the f32 MFMA path hides its LDS + global
-// latency only with >= 3-4 waves per SIMD, i.e. >= ~1024 four-wave workgroups in flight, so small-M
-// layers (P4/P5 at batch 1: M = 1600 / 400) are split along K.
-template <typename T>
-ConvCfg choose_cfg(const ConvArgs& a, long long ws_bytes) {
-  constexpr int V = ElemTraits<T>::kVec;
-  ConvCfg c;
-  c.rb = (a.Cin % (8 * V) == 0) ? 128 : 64;
-  int bke = (c.rb / 16) * V;
-  c.aligned = (a.Cin % bke) == 0;
-  c.cin_tiles = c.aligned ? a.Cin / bke : 1;
-  c.ktiles = (a.K + bke - 1) / bke;
-  c.bn = a.Cout > 64 ? 128 : 64;
-  c.bm = 128;
+// Tile / split-K choice of the register-staged kernels (V = elements per 16-byte vector: 4 for f32, 8 for f16).  MI355X has
+// 256 CUs x 4 SIMDs; the f32 MFMA path hides its LDS + global latency only with >= 3-4 waves per SIMD, i.e. >= ~1024 four-wave
+// workgroups in flight, so small-M layers (P4/P5 at batch 1: M = 1600 / 400) are split along K.  force_tile (OMNI_OP_CONV i22,
+// 0 = the heuristic) replaces the tile only; the K-slice rule and the split-K choice follow from the tile as they do unforced.
+int plan_typed(ConvArgs& a, int V, long long ws_bytes, int force_tile, ConvPlan& p) {
+  int bn = a.Cout > 64 ? 128 : 64, bm = 128;
   auto blocks = [&](int m, int n) { return (long long)((a.M + m - 1) / m) * ((a.Cout + n - 1) / n); };
-  if (blocks(c.bm, c.bn) < 1024 && c.bn == 128) c.bn = 64;
-  if (blocks(c.bm, c.bn) < 1024) c.bm = 64;
+  if (blocks(bm, bn) < 1024 && bn == 128) bn = 64;
+  if (blocks(bm, bn) < 1024) bm = 64;
+  if (force_tile) {
+    OMNI_REQUIRE(force_tile >= 1 && force_tile <= 3, "conv: bad tile code %d (1 = 64x64, 2 = 128x64, 3 = 128x128)", force_tile);
+    bm = force_tile == 1 ? 64 : 128;
+    bn = force_tile == 3 ? 128 : 64;
+  }
   // 128-row tiles: 64-byte K slices keep LDS at 40 KB -> 3 workgroups per CU (measured +8..25 % over 128-byte
   // slices at 2 per CU); 64x64 tiles keep 128-byte slices (fewer barriers, LDS is not the limiter there)
-  if (c.bm == 128) {
-    if (c.rb == 128) {
-      c.rb = 64;
-      bke = (c.rb / 16) * V;
-      c.aligned = (a.Cin % bke) == 0;
-      c.cin_tiles = c.aligned ? a.Cin / bke : 1;
-      c.ktiles = (a.K + bke - 1) / bke;
-    }
-  }
-  long long nb = blocks(c.bm, c.bn);
-  c.splits = 1;
+  const int rb = (bm == 64 && a.Cin % (8 * V) == 0) ? 128 : 64;
+  const int bke = (rb / 16) * V;
+  const bool aligned = (a.Cin % bke) == 0;
+  a.cin_tiles = aligned ? a.Cin / bke : 1;
+  a.ktiles = (a.K + bke - 1) / bke;
+  long long nb = blocks(bm, bn);
+  a.splits = 1;
   if (nb < 768 && a.ws) {
     int want = (int)((1024 + nb - 1) / nb);
-    int maxs = c.ktiles / 4;                 // keep >= 4 K slices per split
+    int maxs = a.ktiles / 4;                 // keep >= 4 K slices per split
     if (maxs > 32) maxs = 32;
     long long cap = ws_bytes / ((long long)a.M * a.Cout * 4);
     if (maxs > cap) maxs = (int)cap;
-    c.splits = want < maxs ? want : maxs;
-    if (c.splits < 2) c.splits = 1;
+    a.splits = want < maxs ? want : maxs;
+    if (a.splits < 2) a.splits = 1;
   }
-  c.kt_per_split = (c.ktiles + c.splits - 1) / c.splits;
-  c.splits = (c.ktiles + c.kt_per_split - 1) / c.kt_per_split;   // no empty splits
-  return c;
+  a.kt_per_split = (a.ktiles + a.splits - 1) / a.splits;
+  a.splits = (a.ktiles + a.kt_per_split - 1) / a.kt_per_split;   // no empty splits
+  a.cnt = nullptr;                                                // split-K of these kernels always takes the reduce launch
+  const bool pw = aligned && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo;
+  p.family = V == 4 ? CONV_FAMILY_F32 : CONV_FAMILY_F16;
+  p.bm = bm; p.bn = bn; p.rb = rb;
+  p.loader = pw ? CONV_LOADER_POINTWISE : aligned ? CONV_LOADER_ALIGNED : CONV_LOADER_GENERIC;
+  p.waves = 4;
+  return OMNI_OK;
 }
 
 template <typename T>
-void launch_typed(ConvArgs& a, long long ws_bytes, hipStream_t s) {
-  ConvCfg c = choose_cfg<T>(a, ws_bytes);
-  a.cin_tiles = c.cin_tiles; a.ktiles = c.ktiles; a.splits = c.splits; a.kt_per_split = c.kt_per_split;
-  if (c.rb == 128) {
-    if (c.bm == 128 && c.bn == 128) launch_cfg<T, 128, 128, 128>(a, c.aligned, s);
-    else if (c.bm == 128 && c.bn == 64) launch_cfg<T, 128, 64, 128>(a, c.aligned, s);
-    else launch_cfg<T, 64, 64, 128>(a, c.aligned, s);
-  } else {
-    if (c.bm == 128 && c.bn == 128) launch_cfg<T, 128, 128, 64>(a, c.aligned, s);
-    else if (c.bm == 128 && c.bn == 64) launch_cfg<T, 128, 64, 64>(a, c.aligned, s);
-    else launch_cfg<T, 64, 64, 64>(a, c.aligned, s);
-  }
+int launch_typed(ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  if (p.rb == 128) return launch_cfg<T, 64, 64, 128>(a, p, s);      // plan_typed: 128-row tiles always walk 64-byte slices
+  if (p.bm == 128 && p.bn == 128) return launch_cfg<T, 128, 128, 64>(a, p, s);
+  if (p.bm == 128 && p.bn == 64) return launch_cfg<T, 128, 64, 64>(a, p, s);
+  return launch_cfg<T, 64, 64, 64>(a, p, s);
 }
 
-}  // namespace
-
-int omni_launch_conv(const omni_op_t* op, hipStream_t s) {
-  ConvArgs a{};
+// op -> validated ConvArgs + the launch choice; no device work (omni_debug_conv_cfg calls it without a GPU)
+int plan_conv(const omni_op_t* op, ConvArgs& a, ConvPlan& p) {
   a.x = op->p[0]; a.w = op->p[1]; a.bias = (const float*)op->p[2]; a.res = op->p[3]; a.y = op->p[4];
   a.B = op->i[0]; a.H = op->i[1]; a.W = op->i[2]; a.Cin = op->i[3]; a.ldi = op->i[4]; a.in_coff = op->i[5];
   a.KH = op->i[6]; a.KW = op->i[7]; a.stride = op->i[8]; a.pad = op->i[9]; a.Ho = op->i[10]; a.Wo = op->i[11];
@@ -819,11 +819,44 @@ int omni_launch_conv(const omni_op_t* op, hipStream_t s) {
   if (op->i[20]) {        // split-f16 weights ([Cout][K/16][16 hi | 16 lo]) + f32 activations
     OMNI_REQUIRE(op->dtype == OMNI_F32 && a.Cin % 32 == 0, "conv: split-f16 mode needs f32 activations and Cin %% 32 == 0");
     OMNI_REQUIRE(op->i[24] >= 0 && (op->i[24] == 0 || op->p[6]), "conv: i24 arrival counters without p6");
-    int rc = launch_split(a, ws_bytes, s, op->i[22], op->i[23], op->i[24] > 0 ? (int*)op->p[6] : nullptr, op->i[24]);
+    return plan_split(a, ws_bytes, op->i[22], op->i[23], op->i[24] > 0 ? (int*)op->p[6] : nullptr, op->i[24], p);
+  }
+  return plan_typed(a, V, ws_bytes, op->i[22], p);
+}
+
+}  // namespace
+
+int omni_launch_conv(const omni_op_t* op, hipStream_t s) {
+  ConvArgs a{};
+  ConvPlan p{};
+  int rc = plan_conv(op, a, p);
+  if (rc) return rc;
+  if (p.family == CONV_FAMILY_SPLIT) {
+    if (p.bm == 128 && p.bn == 128) launch_split_cfg<128, 128>(a, p, s);
+    else if (p.bm == 128 && p.bn == 64) launch_split_cfg<128, 64>(a, p, s);
+    else launch_split_cfg<64, 64>(a, p, s);
+  } else {
+    rc = p.family == CONV_FAMILY_F32 ? launch_typed<float>(a, p, s) : launch_typed<half_t>(a, p, s);
     if (rc) return rc;
-  } else if (op->dtype == OMNI_F32) launch_typed<float>(a, ws_bytes, s);
-  else launch_typed<half_t>(a, ws_bytes, s);
+  }
   OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
+// What omni_launch_conv would launch for `op` (plan_conv, the launcher's own choice); host only, nothing is dereferenced.
+//   out[0] kernel family (0 = conv_igemm_kernel f32, 1 = conv_igemm_kernel f16, 2 = conv_split_kernel)   out[1..3] BM, BN, RB
+//   out[4] loader (0 generic, 1 aligned, 2 pointwise, 3 row-patch)   out[5] splits
+//   out[6] 0 = no split-K, 1 = reduce launch, 2 = in-launch combine   out[7] waves per workgroup
+extern "C" int omni_debug_conv_cfg(const omni_op_t* op, int out[8]) {
+  OMNI_REQUIRE(op && out, "omni_debug_conv_cfg: null argument");
+  OMNI_REQUIRE(op->kind == OMNI_OP_CONV && op->i[20] != 2, "omni_debug_conv_cfg: not a register-staged conv op (kind %d, i20 = %d)", op->kind, op->i[20]);
+  ConvArgs a{};
+  ConvPlan p{};
+  int rc = plan_conv(op, a, p);
+  if (rc) return rc;
+  out[0] = p.family; out[1] = p.bm; out[2] = p.bn; out[3] = p.rb; out[4] = p.loader; out[5] = a.splits;
+  out[6] = a.splits > 1 ? (a.cnt ? 2 : 1) : 0;
+  out[7] = p.waves;
   return OMNI_OK;
 }
 
