@@ -314,8 +314,55 @@ enum {
    *  3 k T * 4 bytes of LDS <= 48 KB.  The model-level entry points (omni_captioner_*) and plan bundles stay greedy.
    *  Value 25: the next enumerator after OMNI_OP_MLP_FUSED (implicit, so the explicitly numbered kinds 1..24 stay the list they were). */
   OMNI_OP_BEAM_STEP,
-  OMNI_OP__COUNT
+  OMNI_OP__COUNT,   /* = 26: one past the implicitly numbered kinds above.  Kinds added since follow with explicit values (this line
+                     * stays directly behind OMNI_OP_BEAM_STEP, where callers and tests expect it); OMNI_OP__END is one past the last kind */
+  /* greedy decoding step WITH GENERATION CONTROLS: OMNI_OP_GREEDY_STEP's generating form (p0..p6 and i0..i11 mean exactly what they
+   * mean there, p4 = token log-probabilities included; p5 must be NULL: there is no target-score form) plus the deterministic
+   * logits processors a transformers caller sets per call, read from DEVICE memory at run time — one captured step graph serves
+   * every setting, nothing is baked into a plan:
+   *  p7 control block (layout below, 4-byte aligned)   i12 its size in bytes
+   * Per row, in transformers' order (generation/utils.py _get_logits_processor), on x = logits + final_logits_bias in f32:
+   *  1 RepetitionPenalty: every token that occurs in ids[b][0..st] (the decoder start token included), once however often it
+   *    occurs: x < 0 ? x * penalty : x / penalty (f32, IEEE divide)
+   *  2 NoRepeatNGram with the block's n-gram size; -1 = the op's i5 (the checkpoint's value), 0 = off
+   *  3 NoBadWords: entry [t0..tk] (k >= 1) puts tk at -inf when k + 1 <= st + 1 and the last k tokens of the history equal t0..tk-1
+   *    (single-token entries are folded into the suppress bitmap by the host)
+   *  4 MinNewTokensLength: eos (i7) at -inf while st < min_new_tokens
+   *  5 ForcedBOS / ForcedEOS as in OMNI_OP_GREEDY_STEP (the forced token, log-probability 0)
+   *  6 SuppressTokens: the suppress bitmap, at every step
+   *  7 SuppressTokensAtBegin: the begin-suppress bitmap at st + 1 == begin_index only
+   * then the arg-max (lowest index among equals), id 0 for a row without a finite entry, pad for finished rows, the EOS bookkeeping
+   * and, with p4, log_softmax(processed)[id] in a second pass that recomputes the same processed values.
+   * Control block, 4-byte words (struct omni_gen_ctrl is the header):
+   *  word 0 f32 repetition penalty (1.0 = none)   1 i32 n-gram size (-1 = i5)   2 i32 min_new_tokens   3 i32 begin_index
+   *  4 i32 n = number of bad-word sequences (0..OMNI_GEN_CTRL_MAX_BAD)   5 i32 stride = words per sequence, 1 + Lmax with
+   *  Lmax <= OMNI_GEN_CTRL_MAX_BAD_LEN (0 when n = 0)   6, 7 reserved (0)
+   *  then u32[W] suppress bitmap, u32[W] begin-suppress bitmap, W = (i1 + 31) / 32 (bit v & 31 of word v >> 5 = token v),
+   *  then i32[n][stride] bad-word table, every row {length L (2..Lmax), t0 .. tL-1, unused}.
+   * i12 >= 32 + 8 W + 4 n stride, with n and stride as the header in p7 holds them when omni_op_launch / omni_plan_create see the
+   * op (they read the 32-byte header back), else OMNI_E_ARG; with the pointer check on, p7 + i12 lies inside one allocation.  The
+   * kernel itself never reads beyond i12 bytes whatever the block says later: sequences that do not fit are not read.
+   * One kernel, greedy_ctrl_step_kernel, always: the bitmap (long-history) form of the n-gram ban — the n-gram size is not known
+   * when the op is recorded — with a second bitmap of the tokens seen.  LDS: (2 W + i3 + 64) x 4 bytes + the reduction arrays
+   * <= 48 KiB, else OMNI_E_ARG (17 KB at a vocabulary of 51289 and T = 1025).  A neutral block (penalty 1.0, n-gram -1, nothing else
+   * set) gives bit for bit what OMNI_OP_GREEDY_STEP gives.  Value 26; plan bundles and the model-level entry points do not use it. */
+  OMNI_OP_GREEDY_CTRL_STEP = OMNI_OP__COUNT,   /* 26, the number the end mark of the list above has */
+  OMNI_OP__END
 };
+
+/* header of the control block of OMNI_OP_GREEDY_CTRL_STEP (p7); the variable parts follow it, see the op */
+#define OMNI_GEN_CTRL_HEADER_BYTES 32
+#define OMNI_GEN_CTRL_MAX_BAD 64       /* multi-token bad-word sequences */
+#define OMNI_GEN_CTRL_MAX_BAD_LEN 8    /* tokens per sequence */
+typedef struct omni_gen_ctrl {
+  float penalty;           /* repetition penalty, > 0; 1.0 = none */
+  int32_t ngram;           /* no_repeat_ngram_size; -1 = the op's i5, 0 = off */
+  int32_t min_new_tokens;  /* eos is -inf while fewer tokens than this have been generated */
+  int32_t begin_index;     /* history length (start token included) at which the begin-suppress bitmap applies */
+  int32_t n_bad;           /* rows of the bad-word table */
+  int32_t bad_stride;      /* 4-byte words per row of the bad-word table */
+  int32_t reserved[2];
+} omni_gen_ctrl_t;
 
 /* candidate record shared by DETECT_DECODE and NMS (32 bytes) */
 typedef struct omni_cand {

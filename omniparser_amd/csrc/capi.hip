@@ -72,7 +72,7 @@ static int dispatch(const omni_op_t* op, hipStream_t s) {
     case OMNI_OP_DWCONV3_LN: return omni_launch_dwconv3_ln(op, s);
     case OMNI_OP_ATTN_ROWS: case OMNI_OP_CHAN_ATTN: case OMNI_OP_ATTN_DECODE: return omni_launch_attention(op, s);
     case OMNI_OP_PROJ_PREP: case OMNI_OP_ASSEMBLE: case OMNI_OP_EMBED_STEP: case OMNI_OP_GREEDY_STEP:
-    case OMNI_OP_BEAM_STEP: case OMNI_OP_CROP_RESIZE: return omni_launch_misc(op, s);
+    case OMNI_OP_BEAM_STEP: case OMNI_OP_GREEDY_CTRL_STEP: case OMNI_OP_CROP_RESIZE: return omni_launch_misc(op, s);
     default:
       omni_set_error("unknown op kind %d", op->kind);
       return OMNI_E_ARG;
@@ -144,6 +144,16 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
         ext[6] = 4;
       }
       break;
+    case OMNI_OP_GREEDY_CTRL_STEP: {                         // whole buffers; p7: the i12 bytes of the control block
+      const long long rows = i[0], T = i[3];
+      ext[0] = rows > 0 ? ((rows - 1) * i[2] + i[1]) * esz : 1;
+      ext[1] = (long long)i[1] * 4;
+      ext[2] = ext[4] = rows * T * 4;
+      ext[3] = rows * 4;
+      ext[6] = 4;
+      ext[7] = i[12];
+      break;
+    }
     case OMNI_OP_MLP_FUSED: {
       const long long rows = (long long)i[0] * i[1], C = i[3], hid = i[12];
       ext[0] = span(rows, i[4], i[5], C); ext[1] = hid * C * 4; ext[2] = hid * 4; ext[3] = span(rows, i[16], i[17], C);
@@ -251,9 +261,43 @@ static int check_op_ptrs(const omni_op_t* op, int index) {
   return OMNI_OK;
 }
 
+// OMNI_OP_GREEDY_CTRL_STEP: i12 must cover what the header of the control block (p7, device memory) claims — the header, two bitmaps
+// over the vocabulary i1 and n_bad rows of bad_stride words.  The 32-byte header is read back here, once per single-op launch / per
+// plan creation (never inside a capture: a captured plan replays its launches without coming through here); the pointer check, where
+// it is on, has already placed p7 + i12 inside one allocation.  The kernel clamps on its own whatever the block holds later.
+static int check_ctrl_block(const omni_op_t* op, int index) {
+  if (op->kind != OMNI_OP_GREEDY_CTRL_STEP) return OMNI_OK;
+  const long long bytes = op->i[12], nw = ((long long)op->i[1] + 31) >> 5, fixed = OMNI_GEN_CTRL_HEADER_BYTES + 8 * nw;
+  if (!op->p[7] || op->i[1] <= 0 || bytes < fixed) {
+    omni_set_error("op %d (greedy_ctrl_step): a control block of %lld bytes (i12) at p7 = %p cannot hold the header and two bitmaps over a "
+                   "vocabulary of %d (%lld bytes)", index, bytes, op->p[7], op->i[1], fixed);
+    return OMNI_E_ARG;
+  }
+  omni_gen_ctrl_t h;
+  hipError_t e = hipMemcpy(&h, op->p[7], sizeof h, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    omni_set_error("op %d (greedy_ctrl_step): the header of the control block p7 = %p cannot be read (%s)", index, op->p[7], hipGetErrorString(e));
+    return OMNI_E_ARG;
+  }
+  if (h.n_bad < 0 || h.n_bad > OMNI_GEN_CTRL_MAX_BAD || (h.n_bad > 0 && (h.bad_stride < 3 || h.bad_stride > OMNI_GEN_CTRL_MAX_BAD_LEN + 1))) {
+    omni_set_error("op %d (greedy_ctrl_step): the control block claims %d bad-word sequences of stride %d (at most %d of 2..%d tokens)", index,
+                   h.n_bad, h.bad_stride, OMNI_GEN_CTRL_MAX_BAD, OMNI_GEN_CTRL_MAX_BAD_LEN);
+    return OMNI_E_ARG;
+  }
+  const long long need = fixed + 4LL * h.n_bad * h.bad_stride;
+  if (bytes < need) {
+    omni_set_error("op %d (greedy_ctrl_step): the control block's header claims %d bad-word sequences of stride %d = %lld bytes, i12 says %lld",
+                   index, h.n_bad, h.bad_stride, need, bytes);
+    return OMNI_E_ARG;
+  }
+  return OMNI_OK;
+}
+
 extern "C" int omni_op_launch(const omni_op_t* op, void* stream) {
   if (!op) { omni_set_error("omni_op_launch: null op"); return OMNI_E_ARG; }
   if (check_ptrs_enabled()) { int rc = check_op_ptrs(op, 0); if (rc) return rc; }
+  if (int rc = check_ctrl_block(op, 0)) return rc;
   return dispatch(op, (hipStream_t)stream);
 }
 
@@ -266,13 +310,14 @@ struct omni_plan {
 extern "C" int omni_plan_create(const omni_op_t* ops, int n_ops, omni_plan_t** out) {
   if (!ops || n_ops <= 0 || !out) { omni_set_error("omni_plan_create: bad arguments"); return OMNI_E_ARG; }
   for (int i = 0; i < n_ops; ++i) {
-    if (ops[i].kind <= 0 || ops[i].kind >= OMNI_OP__COUNT) {
+    if (ops[i].kind <= 0 || ops[i].kind >= OMNI_OP__END) {
       omni_set_error("omni_plan_create: op %d has unknown kind %d", i, ops[i].kind);
       return OMNI_E_ARG;
     }
   }
   if (check_ptrs_enabled())
     for (int i = 0; i < n_ops; ++i) { int rc = check_op_ptrs(&ops[i], i); if (rc) return rc; }
+  for (int i = 0; i < n_ops; ++i) { int rc = check_ctrl_block(&ops[i], i); if (rc) return rc; }
   omni_plan* p = new omni_plan();
   p->ops.assign(ops, ops + n_ops);
   *out = p;

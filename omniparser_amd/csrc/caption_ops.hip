@@ -12,6 +12,7 @@
 //   embed_step     decoder token embedding + learned position (offset 2)           bart:80-98,594-640
 //   attn_decode    single-query attention with KV-cache append (self) / fixed K,V (cross)
 //   greedy_step    final_logits_bias + NoRepeatNGram + ForcedBOS/EOS + argmax + EOS/pad bookkeeping
+//   greedy_ctrl_step  the same with the per-call generation controls read from a control block in device memory
 //   beam_step      the same processors on log-probs + top-2k + running / finished beam bookkeeping (hf _beam_search)
 //                  hf:generation/utils.py:2783-2937, hf:generation/logits_process.py:1115-1139,1556,1601
 //   crop_resize    crop -> cv2.resize(64x64, INTER_LINEAR) -> [PIL BICUBIC to RxR] -> /255, normalise
@@ -2244,6 +2245,146 @@ __global__ __launch_bounds__(256) void greedy_step_long_kernel(GreedyArgs a) {
   }
 }
 
+// OMNI_OP_GREEDY_CTRL_STEP: the long-history form above plus the per-call generation controls, all read from the control block in
+// device memory (include/omni_amd.h: struct omni_gen_ctrl, two vocabulary bitmaps, the bad-word table) — nothing of them is a launch
+// argument, so one captured graph serves every setting.  LDS: `bm` [(V + 31) / 32][2], per 32 tokens the word of everything that ends
+// at -inf (suppress bitmap, begin-suppress bitmap at begin_index, EOS below min_new_tokens, then the followers of matching n-grams and
+// the last tokens of matching bad-word sequences) next to the word of the tokens SEEN in the history (repetition penalty, once per
+// token) — interleaved so that a row entry costs one LDS access, `follow`
+// [T + 64] the list both are folded from (first the bans, then the staged history).  Word w of either bitmap belongs to thread w & 255, as above: no atomics on the bitmaps,
+// no dependence on the order of the list.  Both passes over the row compute the same processed value (`proc`).  The block is never
+// read beyond `ctrl_bytes`: the launcher checks that the header and the bitmaps fit, and sequences that do not fit are not read.
+struct GreedyCtrlArgs {
+  GreedyArgs g;
+  const unsigned* ctrl; int ctrl_bytes;
+};
+
+template <typename T, bool SCORES>
+__global__ __launch_bounds__(256) void greedy_ctrl_step_kernel(GreedyCtrlArgs c) {
+  OMNI_DYN_LDS(unsigned, bm);          // [nw][2] {-inf word, seen word}, [T + 64] followers / last tokens of matching sequences
+  __shared__ float sval[256];
+  __shared__ int sidx[256];
+  __shared__ int nmatch;
+  const GreedyArgs& a = c.g;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int st = *a.step;              // tokens so far = st + 1 (ids[b][0..st]); we write ids[b][st+1]
+  if (st < 0 || st + 1 >= a.T) return; // a step outside the plan's positions writes nothing (uniform over the grid)
+  int* ids = a.ids + b * a.T;
+  const int cur_len = st + 1;
+  const int nw = (a.V + 31) >> 5;
+  int* follow = (int*)(bm + 2 * nw);
+  const omni_gen_ctrl_t* h = (const omni_gen_ctrl_t*)c.ctrl;
+  const float penalty = h->penalty;
+  const int n = h->ngram < 0 ? a.ngram : h->ngram;
+  const unsigned* supp = c.ctrl + OMNI_GEN_CTRL_HEADER_BYTES / 4;
+  const unsigned* begin = supp + nw;
+  const int* table = (const int*)(begin + nw);
+  const int stride = h->bad_stride;
+  int nbad = 0;
+  if (stride >= 2 && stride <= OMNI_GEN_CTRL_MAX_BAD_LEN + 1) {
+    const int room = (c.ctrl_bytes - OMNI_GEN_CTRL_HEADER_BYTES - 8 * nw) / (4 * stride);     // whole rows inside the block
+    nbad = max(0, min(min(h->n_bad, OMNI_GEN_CTRL_MAX_BAD), room));
+  }
+  const bool at_begin = cur_len == h->begin_index;
+  const int eos_word = st < h->min_new_tokens && a.eos >= 0 && a.eos < a.V ? a.eos >> 5 : -1;   // MinNewTokensLength
+  for (int w = tid; w < nw; w += 256) {
+    bm[2 * w] = supp[w] | (at_begin ? begin[w] : 0u) | (w == eos_word ? 1u << (a.eos & 31) : 0u);
+    bm[2 * w + 1] = 0u;
+  }
+  if (tid == 0) nmatch = 0;
+  __syncthreads();
+  // NoRepeatNGram: ban tokens completing an n-gram already generated (incl. decoder start token)
+  const int nstart = n > 0 && cur_len + 1 >= n ? min(cur_len - n + 1, a.T) : 0;     // start positions i with i + n - 1 < cur_len
+  for (int i = tid; i < nstart; i += 256) {
+    bool match = true;
+    for (int j = 0; j < n - 1; ++j)
+      if (ids[i + j] != ids[cur_len - (n - 1) + j]) { match = false; break; }
+    const int f = ids[i + n - 1];
+    if (match && f >= 0 && f < a.V) follow[atomicAdd(&nmatch, 1)] = f;
+  }
+  // NoBadWords: sequence [t0..tk] bans tk when the history holds at least k + 1 tokens and ends in t0..tk-1
+  if (tid < nbad) {
+    const int* row = table + tid * stride;
+    const int len = row[0];
+    if (len >= 1 && len < stride && len <= cur_len) {
+      bool match = true;
+      for (int j = 0; j < len - 1; ++j)
+        if (ids[cur_len - (len - 1) + j] != row[1 + j]) { match = false; break; }
+      const int f = row[len];
+      if (match && f >= 0 && f < a.V) follow[atomicAdd(&nmatch, 1)] = f;
+    }
+  }
+  __syncthreads();
+  const int nm = nmatch;
+  for (int q = 0; q < nm; ++q) {
+    const int f = follow[q];
+    if (((f >> 5) & 255) == tid) bm[2 * (f >> 5)] |= 1u << (f & 31);
+  }
+  __syncthreads();
+  // RepetitionPenalty: the tokens of the history, each once.  The history is staged in the list (its bans are folded by now) so that
+  // the 256 scans over it read LDS instead of global memory
+  for (int q = tid; q < cur_len; q += 256) follow[q] = ids[q];
+  __syncthreads();
+  for (int q = 0; q < cur_len; ++q) {
+    const int f = follow[q];
+    if (f >= 0 && f < a.V && ((f >> 5) & 255) == tid) bm[2 * (f >> 5) + 1] |= 1u << (f & 31);
+  }
+  __syncthreads();
+  int forced = -1;
+  if (a.forced_bos >= 0 && cur_len == 1) forced = a.forced_bos;
+  if (a.forced_eos >= 0 && cur_len == a.max_new) forced = a.forced_eos;   // max_length - 1 == max_new (start token + max_new)
+  int tok;
+  [[maybe_unused]] float lp = 0.0f;
+  if (forced >= 0) {
+    tok = forced;
+  } else {
+    const T* lg = (const T*)a.logits + (long long)b * a.ldl;
+    auto proc = [&](int v) {
+      float x = ldf(lg + v) + (a.bias ? a.bias[v] : 0.0f);
+      const unsigned bit = 1u << (v & 31);
+      const unsigned ban = bm[2 * (v >> 5)], seen = bm[2 * (v >> 5) + 1];       // one 8-byte pair: both words of the token
+      if (seen & bit) x = x < 0.0f ? x * penalty : x / penalty;                 // branched on: the IEEE divide is paid by seen tokens only
+      return (ban & bit) ? -INFINITY : x;
+    };
+    float best = -INFINITY; int bi = 0x7fffffff;
+    for (int v = tid; v < a.V; v += 256) {
+      const float x = proc(v);
+      if (x > best) { best = x; bi = v; }      // first max within this thread's ascending stride
+    }
+    sval[tid] = best; sidx[tid] = bi;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) {
+        float ov = sval[tid + s]; int oi = sidx[tid + s];
+        if (ov > sval[tid] || (ov == sval[tid] && oi < sidx[tid])) {
+          sval[tid] = ov; sidx[tid] = oi;
+        }
+      }
+      __syncthreads();
+    }
+    tok = sidx[0];
+    // no entry compared greater than -inf (all NaN / -inf / suppressed): position 0, as greedy_step_kernel and torch.argmax
+    if (tok < 0 || tok >= a.V) tok = 0;
+    if constexpr (SCORES) {
+      const float mx = sval[0];                 // the processed row's maximum (-inf for a degenerate row: lp is then unspecified)
+      __syncthreads();                          // every thread holds mx and tok before sval is reused
+      float sum = 0.f;
+      for (int v = tid; v < a.V; v += 256) sum += expf(proc(v) - mx);
+      sum = wave_sum(sum);
+      if ((tid & 63) == 0) sval[tid >> 6] = sum;
+      __syncthreads();
+      lp = -logf(((sval[0] + sval[1]) + sval[2]) + sval[3]);
+    }
+  }
+  if (tid == 0) {
+    int fin = a.finished[b];
+    if (fin) tok = a.pad;                       // finished rows keep emitting pad (hf utils.py:2925-2929)
+    ids[st + 1] = tok;
+    if constexpr (SCORES) a.logp[(long long)b * a.T + st + 1] = fin ? 0.0f : lp;
+    if (!fin && tok == a.eos) a.finished[b] = 1;
+  }
+}
+
 __global__ void step_inc_kernel(int* step) { if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1; }
 
 // ------------------------------------------------------------------------------------ score_step (OMNI_OP_GREEDY_STEP p5)
@@ -2933,6 +3074,37 @@ static int launch_greedy(const omni_op_t* op, hipStream_t s) {
   return OMNI_OK;
 }
 
+// OMNI_OP_GREEDY_CTRL_STEP: the generating form of launch_greedy with the control block p7 (i12 bytes); one kernel for every setting
+static int launch_greedy_ctrl(const omni_op_t* op, hipStream_t s) {
+  GreedyCtrlArgs c{};
+  GreedyArgs& a = c.g;
+  a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (int*)op->p[2]; a.finished = (int*)op->p[3];
+  a.step = (const int*)op->p[6];
+  a.B = op->i[0]; a.V = op->i[1]; a.ldl = op->i[2]; a.T = op->i[3]; a.max_new = op->i[4]; a.ngram = op->i[5];
+  a.bos = op->i[6]; a.eos = op->i[7]; a.pad = op->i[8]; a.forced_bos = op->i[9]; a.forced_eos = op->i[10];
+  a.logp = (float*)op->p[4];
+  c.ctrl = (const unsigned*)op->p[7]; c.ctrl_bytes = op->i[12];
+  OMNI_REQUIRE(a.logits && a.ids && a.finished && a.step && a.B > 0 && a.V > 0 && a.ldl >= a.V && a.T >= a.max_new + 1 && a.max_new >= 1,
+               "greedy_ctrl_step: bad arguments");
+  OMNI_REQUIRE(!op->p[5], "greedy_ctrl_step: p5 (target lengths) belongs to OMNI_OP_GREEDY_STEP; the controls have no target-score form");
+  OMNI_REQUIRE(c.ctrl && (unsigned long long)c.ctrl % 4 == 0, "greedy_ctrl_step: p7 (control block) is NULL or not 4-byte aligned");
+  const long long nw = ((long long)a.V + 31) >> 5;
+  OMNI_REQUIRE(c.ctrl_bytes >= OMNI_GEN_CTRL_HEADER_BYTES + 8 * nw, "greedy_ctrl_step: a control block of %d bytes (i12) cannot hold the header and "
+               "two bitmaps over a vocabulary of %d (%lld bytes)", c.ctrl_bytes, a.V, OMNI_GEN_CTRL_HEADER_BYTES + 8 * nw);
+  const size_t lds = ((size_t)2 * nw + (size_t)a.T + OMNI_GEN_CTRL_MAX_BAD) * 4;
+  OMNI_REQUIRE(lds <= 48 * 1024, "greedy_ctrl_step: a vocabulary of %d and %d positions exceed the bitmap LDS", a.V, a.T);
+  int rc = a.logp ? by_dtype(op->dtype, "greedy_ctrl_step",
+      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<float, true>), dim3(a.B), dim3(256), lds, s, c); },
+      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<half_t, true>), dim3(a.B), dim3(256), lds, s, c); })
+                  : by_dtype(op->dtype, "greedy_ctrl_step",
+      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<float, false>), dim3(a.B), dim3(256), lds, s, c); },
+      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<half_t, false>), dim3(a.B), dim3(256), lds, s, c); });
+  if (rc) return rc;
+  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
+  OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
 static int launch_beam(const omni_op_t* op, hipStream_t s) {
   BeamArgs a{};
   a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (int*)op->p[2]; a.run_score = (float*)op->p[3];
@@ -3022,6 +3194,7 @@ int omni_launch_misc(const omni_op_t* op, hipStream_t s) {
   switch (op->kind) {
     case OMNI_OP_GREEDY_STEP: return launch_greedy(op, s);
     case OMNI_OP_BEAM_STEP: return launch_beam(op, s);
+    case OMNI_OP_GREEDY_CTRL_STEP: return launch_greedy_ctrl(op, s);
     case OMNI_OP_CROP_RESIZE: return launch_crop_resize(op, s);
     case OMNI_OP_PROJ_PREP: case OMNI_OP_ASSEMBLE: case OMNI_OP_EMBED_STEP: return launch_glue(op, s);
     default: omni_set_error("misc: bad kind %d", op->kind); return OMNI_E_ARG;

@@ -270,6 +270,146 @@ def caption_confidence(ids_row, logp_row, eos, forced_bos, forced_eos, max_new):
     return float(math.exp(sum(vals) / len(vals)))
 
 
+# ---- generation controls (OMNI_OP_GREEDY_CTRL_STEP): the ONE Python mirror of the control block of include/omni_amd.h
+GEN_CTRL_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens",
+                 "bad_words_ids")
+GEN_CTRL_HEADER_WORDS = 8          # struct omni_gen_ctrl: f32 penalty | i32 ngram | min_new_tokens | begin_index | n_bad | bad_stride | 0 | 0
+GEN_CTRL_MAX_BAD = 64              # OMNI_GEN_CTRL_MAX_BAD: multi-token bad-word sequences
+GEN_CTRL_MAX_BAD_LEN = 8           # OMNI_GEN_CTRL_MAX_BAD_LEN: tokens per sequence
+
+
+def gen_ctrl_words(vocab: int, n_bad: int = GEN_CTRL_MAX_BAD, stride: int = GEN_CTRL_MAX_BAD_LEN + 1) -> int:
+    """4-byte words of a control block over `vocab` tokens: header, suppress bitmap, begin-suppress bitmap, n_bad rows of `stride`
+    words (the defaults: the largest block there is, the capacity of a controls plan's buffer)"""
+    return GEN_CTRL_HEADER_WORDS + 2 * ((int(vocab) + 31) // 32) + int(n_bad) * int(stride)
+
+
+class GenerationControls:
+    """The deterministic logits processors of transformers' generate() that a caller sets per call, as one value object:
+    repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, bad_words_ids — applied on
+    the device by OMNI_OP_GREEDY_CTRL_STEP in transformers' order (include/omni_amd.h).  None everywhere = `neutral`: the call
+    runs the plans it always ran.  The constructor checks types and the limits that need no model; `check` the rest (vocabulary,
+    max_new_tokens, the special tokens); `pack` writes the control block."""
+    __slots__ = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens",
+                 "bad_words_ids")
+
+    def __init__(self, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None,
+                 begin_suppress_tokens=None, bad_words_ids=None):
+        isint = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        p = repetition_penalty
+        if p is not None and (isinstance(p, bool) or not isinstance(p, (int, float)) or not p > 0 or math.isinf(p)):
+            raise ValueError(f"repetition_penalty must be a float greater than 0, got {p!r}")
+        self.repetition_penalty = None if p is None else float(p)
+        for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+            if v is not None and (not isint(v) or v < 0):
+                raise ValueError(f"{name} must be an integer of at least 0, got {v!r}")
+        self.no_repeat_ngram_size, self.min_new_tokens = no_repeat_ngram_size, min_new_tokens
+
+        def tokens(name, v):
+            if v is None:
+                return ()
+            if isinstance(v, torch.Tensor):
+                v = v.tolist()
+            if isinstance(v, (str, bytes)) or not hasattr(v, "__iter__"):
+                raise ValueError(f"{name} must be a list of token ids, got {v!r}")
+            v = list(v)
+            bad = [t for t in v if not isint(t) or t < 0]
+            if bad:
+                raise ValueError(f"{name}: token ids must be integers of at least 0, got {bad[0]!r}")
+            return tuple(v)
+        self.suppress_tokens = tokens("suppress_tokens", suppress_tokens)
+        self.begin_suppress_tokens = tokens("begin_suppress_tokens", begin_suppress_tokens)
+        if bad_words_ids is not None and (isinstance(bad_words_ids, (str, bytes)) or not hasattr(bad_words_ids, "__iter__")):
+            raise ValueError(f"bad_words_ids must be a list of token id lists, got {bad_words_ids!r}")
+        words = [tokens("bad_words_ids", w) for w in (bad_words_ids if bad_words_ids is not None else ())]
+        if any(len(w) == 0 for w in words):
+            raise ValueError("bad_words_ids: an empty sequence bans nothing and is refused")
+        long_ = [w for w in words if len(w) > GEN_CTRL_MAX_BAD_LEN]
+        if long_:
+            raise ValueError(f"bad_words_ids: a sequence of {len(long_[0])} tokens (at most {GEN_CTRL_MAX_BAD_LEN})")
+        self.bad_words_ids = tuple(dict.fromkeys(words))          # transformers keys its table by the sequence: duplicates are one entry
+        if len(self._multi()) > GEN_CTRL_MAX_BAD:
+            raise ValueError(f"bad_words_ids: {len(self._multi())} multi-token sequences (at most {GEN_CTRL_MAX_BAD})")
+
+    @classmethod
+    def of(cls, x) -> "GenerationControls":
+        """None -> neutral; a GenerationControls -> itself; a dict of GEN_CTRL_KEYS -> its controls (another key: ValueError)"""
+        if x is None:
+            return cls()
+        if isinstance(x, cls):
+            return x
+        if not isinstance(x, dict):
+            raise ValueError(f"generation controls must be a GenerationControls, a dict of {', '.join(GEN_CTRL_KEYS)}, or None; got {x!r}")
+        unknown = [k for k in x if k not in GEN_CTRL_KEYS]
+        if unknown:
+            raise ValueError(f"unknown generation control {unknown[0]!r} (known: {', '.join(GEN_CTRL_KEYS)})")
+        return cls(**x)
+
+    def _multi(self):
+        return [w for w in self.bad_words_ids if len(w) > 1]
+
+    def _single(self):
+        return [w[0] for w in self.bad_words_ids if len(w) == 1]
+
+    @property
+    def neutral(self) -> bool:
+        """nothing to apply: such a call takes the default plans (same cache key, same ops, same bits)"""
+        return (self.repetition_penalty in (None, 1.0) and self.no_repeat_ngram_size is None and self.min_new_tokens in (None, 0)
+                and not self.suppress_tokens and not self.begin_suppress_tokens and not self.bad_words_ids)
+
+    def check(self, vocab, max_new_tokens, eos, forced_bos=-1, forced_eos=-1):
+        """the checks that need the model: ids inside the vocabulary, min_new_tokens <= max_new_tokens, and no EOS / forced token
+        among the suppressed ones (transformers drops [eos] from bad words by itself; a suppressed forced token makes its forced row
+        all -inf).  ValueError; returns self."""
+        if self.min_new_tokens is not None and self.min_new_tokens > int(max_new_tokens):
+            raise ValueError(f"min_new_tokens must be in 0..max_new_tokens ({max_new_tokens}), got {self.min_new_tokens}")
+        for name, toks in (("suppress_tokens", self.suppress_tokens), ("begin_suppress_tokens", self.begin_suppress_tokens),
+                           ("bad_words_ids", [t for w in self.bad_words_ids for t in w])):
+            bad = [t for t in toks if t >= vocab]
+            if bad:
+                raise ValueError(f"{name}: token id {bad[0]} is outside the vocabulary (0..{vocab - 1})")
+        special = {int(eos): "the EOS token"}
+        if forced_bos is not None and int(forced_bos) >= 0:
+            special.setdefault(int(forced_bos), "the forced BOS token")
+        if forced_eos is not None and int(forced_eos) >= 0:
+            special.setdefault(int(forced_eos), "the forced EOS token")
+        for name, toks in (("suppress_tokens", self.suppress_tokens), ("begin_suppress_tokens", self.begin_suppress_tokens),
+                           ("bad_words_ids (as a single-token entry)", self._single())):
+            hit = [t for t in toks if t in special]
+            if hit:
+                raise ValueError(f"{name}: token {hit[0]} is {special[hit[0]]} and cannot be suppressed")
+        return self
+
+    def pack(self, vocab, forced_bos=-1) -> torch.Tensor:
+        """the control block as i32 words on the host (include/omni_amd.h OMNI_OP_GREEDY_CTRL_STEP): header, suppress bitmap (with
+        the single-token bad words), begin-suppress bitmap, bad-word table {length, tokens..} of stride 1 + the longest sequence.
+        begin_index as transformers computes it for a decoder that starts from one token: 1, or 2 behind a forced BOS."""
+        nw = (int(vocab) + 31) // 32
+        multi = self._multi()
+        stride = 1 + max(len(w) for w in multi) if multi else 0
+        words = torch.zeros(gen_ctrl_words(vocab, len(multi), stride), dtype=torch.int32)
+        words[0:1] = torch.tensor([1.0 if self.repetition_penalty is None else self.repetition_penalty], dtype=torch.float32).view(torch.int32)
+        words[1] = -1 if self.no_repeat_ngram_size is None else self.no_repeat_ngram_size
+        words[2] = self.min_new_tokens or 0
+        words[3] = 2 if forced_bos is not None and int(forced_bos) >= 0 else 1
+        words[4], words[5] = len(multi), stride
+
+        def bitmap(toks):
+            bits = torch.zeros(nw * 32, dtype=torch.int64)
+            if toks:
+                bits[torch.tensor(sorted(set(toks)))] = 1
+            w = (bits.view(nw, 32) << torch.arange(32)).sum(1)                 # < 2^32 in i64
+            return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)   # the same 32 bits as i32
+        o = GEN_CTRL_HEADER_WORDS
+        words[o:o + nw] = bitmap(list(self.suppress_tokens) + self._single())
+        words[o + nw:o + 2 * nw] = bitmap(list(self.begin_suppress_tokens))
+        for q, w in enumerate(multi):
+            r = o + 2 * nw + q * stride
+            words[r] = len(w)
+            words[r + 1:r + 1 + len(w)] = torch.tensor(w, dtype=torch.int32)
+        return words
+
+
 FORCE_ROWS = (1, 4, 8)             # candidate rows per crop of a teacher-forced plan (`Florence2Captioner.score`)
 LABEL_CAPACITIES = (8, 16, 32)     # label tokens per candidate (T - 1 of such a plan)
 
@@ -396,16 +536,20 @@ class _StepPlans:
     beam = None
     logp = None
     force = None
+    ctrl = None
 
-    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None, scores=False, force=None):
+    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None, scores=False, force=None, controls=False):
         """nkeys: i32 [crops] valid encoder keys per crop (a prompt shorter than the plan's text capacity: OMNI_OP_ATTN_DECODE p7 of
-        the cross-attention), or None = all S"""
+        the cross-attention), or None = all S
+        controls (greedy only): the plan owns `ctrl`, an i32 buffer of the largest control block (`gen_ctrl_words`), and ends in
+        OMNI_OP_GREEDY_CTRL_STEP instead of OMNI_OP_GREEDY_STEP; `set_controls` uploads a call's block before its first step"""
         w, dev, dt = cap.w, cap.device, cap.dtype
         sd = w.sd
         D, nh, lm = w.d_model, w.n_heads, "model.language_model."
         self.T = max_new + 1
         self.beam = beam
         assert not (force and (beam or scores)), "a teacher-forced plan neither searches nor generates"
+        assert not (controls and (beam or force)), "generation controls are a greedy-decoding feature"
         self.force = force
         kb = beam[0] if beam else (force or 1)
         crops, B = B, B * kb                               # B = decoder rows from here on
@@ -436,6 +580,13 @@ class _StepPlans:
         assert not (scores and beam), "token scores are a greedy-decoding output (beam search returns sequences_scores)"
         self.logp = pd_.raw((B, T), torch.float32) if scores or force else None
         self.step = pd_.raw((1,), torch.int32)
+        if controls:
+            self.ctrl = pd_.raw((gen_ctrl_words(w.vocab),), torch.int32)
+            self.ctrl.zero_()
+            neutral = GenerationControls().pack(w.vocab, w.forced_bos)
+            self.ctrl[:neutral.numel()].copy_(neutral)
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()       # omni_plan_create reads the block's header back
         esz = 4 if dt == L.F32 else 2
 
         def dlinear(key, xin: View, out: View, act=L.ACT_NONE, res=None, keys=None):
@@ -502,6 +653,13 @@ class _StepPlans:
                                  p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(), None,
                                     self.logp.data_ptr(), self.tlen.data_ptr(), self.step.data_ptr(), self.top1.data_ptr()],
                                  i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 6: w.bos, 7: w.eos, 8: w.pad, 9: -1, 10: -1, 11: 1}))
+        elif controls:                                     # the same slots + the control block, read on the device at every step
+            pd_.add_op(L.make_op(L.OP_GREEDY_CTRL_STEP, dt,
+                                 p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
+                                    self.finished.data_ptr(), self.logp.data_ptr() if scores else None, None, self.step.data_ptr(),
+                                    self.ctrl.data_ptr()],
+                                 i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: w.bos, 7: w.eos, 8: w.pad,
+                                    9: w.forced_bos, 10: w.forced_eos, 11: 1, 12: self.ctrl.numel() * 4}))
         else:
             pd_.add_op(L.make_op(L.OP_GREEDY_STEP, dt,
                                  p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
@@ -553,6 +711,12 @@ class _StepPlans:
         assert self.force and tuple(ids.shape) == tuple(self.ids.shape) and tuple(tlen.shape) == tuple(self.tlen.shape)
         self.ids.copy_(ids, non_blocking=True)
         self.tlen.copy_(tlen, non_blocking=True)
+
+    def set_controls(self, block: torch.Tensor):
+        """a controls plan's block on the current stream: `GenerationControls.pack` words from the host.  Words of the buffer
+        behind the block keep what they held; no header makes the kernel read them."""
+        assert self.ctrl is not None and block.dtype == torch.int32 and block.numel() <= self.ctrl.numel()
+        self.ctrl[:block.numel()].copy_(block, non_blocking=True)
 
     def result_ids(self, n: int) -> torch.Tensor:
         """device ids of the first n crops: the greedy rows, or the best finished hypothesis of each crop"""
@@ -628,7 +792,7 @@ class _CaptionPlans(_StepPlans):
     pad token's embedding, attend to the valid keys, stay finite) and are read by nobody."""
 
     def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None,
-                 beam=None, n_txt=None, scores=False, force=None):
+                 beam=None, n_txt=None, scores=False, force=None, controls=False):
         w, dev, dt = cap.w, cap.device, cap.dtype
         if arena is not None:
             n_txt = arena.n_txt
@@ -925,7 +1089,7 @@ class _CaptionPlans(_StepPlans):
                 self.encode_plan.capture(stream or cap.stream)
             return
         # ---------------- decoder step plan (for a single micro-batch; batches of several micro-batches decode through _DecodePlans)
-        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys, scores=scores, force=force)
+        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys, scores=scores, force=force, controls=controls)
         self._warm_up_and_capture(cap, self.encode_plan, self.step_plan)
 
     def set_prompt(self, ids: torch.Tensor, nkeys: torch.Tensor, n: int):
@@ -1162,12 +1326,16 @@ class Florence2Captioner:
         return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
     @torch.inference_mode()
-    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False, force=None) -> _CaptionPlans:
+    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False, force=None, controls=False) -> _CaptionPlans:
         """slot 1 = a second, independent set of buffers of the same capacity: the pipelined stream (pipeline.py::parse_stream) keeps two
         128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without).
         beam: see `beam_config` (the step plan decodes B k rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`);
-        it is part of the cache key, None = the default prompt's plan."""
+        it is part of the cache key, None = the default prompt's plan.  controls (greedy only): the plan that ends in
+        OMNI_OP_GREEDY_CTRL_STEP and owns a control block (`_StepPlans.set_controls`); part of the cache key beside `scores`, and
+        only ever built by a call with non-neutral `GenerationControls` — one plan serves every setting."""
         self.check_max_new(max_new, beam)
+        if controls and (beam or force):
+            raise ValueError("generation controls are applied by greedy decoding only (no beam search, no teacher-forced scoring)")
         key = (B, R, max_new) if slot == 0 else (B, R, max_new, slot)
         if beam or n_txt is not None:
             key = (B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
@@ -1176,7 +1344,23 @@ class Florence2Captioner:
         if force:                      # teacher-forced scoring of `force` candidate rows per crop, max_new = the label capacity
             key = (B, R, max_new, slot, None) + (() if n_txt is None else (("txt", n_txt),)) + (("force", force, max_new),)
             return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, n_txt=n_txt, force=force))
+        if controls:
+            key = (B, R, max_new, slot, None) + (() if n_txt is None else (("txt", n_txt),)) + (("scores",) if scores else ()) + ("controls",)
+            return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, n_txt=n_txt, scores=scores, controls=True))
         return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
+
+    def generation_controls(self, controls, max_new_tokens, beam=None) -> Optional[GenerationControls]:
+        """`controls` (None, a dict of GEN_CTRL_KEYS or a GenerationControls) checked against this model, before anything touches a
+        device: None when they are neutral (the call is the default call), else the checked object.  ValueError: a bad value
+        (`GenerationControls`, `GenerationControls.check`), or non-neutral controls together with beam search — transformers applies
+        the processors to log-probabilities there, which OMNI_OP_BEAM_STEP does not do."""
+        gc = GenerationControls.of(controls).check(self.w.vocab, max_new_tokens, self.w.eos, self.w.forced_bos, self.w.forced_eos)
+        if gc.neutral:
+            return None
+        if beam:
+            raise ValueError("generation controls (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, "
+                             "begin_suppress_tokens, bad_words_ids) are not supported with beam search (num_beams > 1): greedy decoding only")
+        return gc
 
     # ---- prompts
     def prompt_batch(self, rows, R):
@@ -1328,7 +1512,9 @@ class Florence2Captioner:
 
     @torch.inference_mode()
     def generate(self, input_ids=None, pixel_values=None, max_new_tokens=20, num_beams=1, do_sample=False, num_return_sequences=1,
-                 length_penalty=None, early_stopping=None, return_dict_in_generate=False, attention_mask=None, **kw):
+                 length_penalty=None, early_stopping=None, return_dict_in_generate=False, attention_mask=None,
+                 repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None,
+                 begin_suppress_tokens=None, bad_words_ids=None, **kw):
         """hf-compatible entry point (ref:util/utils.py:125).  pixel_values: [B,3,R,R] float (NCHW).
 
         input_ids [B, n_img + L]: the first n_img = (R / 32)^2 + 1 columns must be the image placeholder token (anything else is a
@@ -1350,7 +1536,24 @@ class Florence2Captioner:
         scores, what transformers' compute_transition_scores(sequences, scores, normalize_logits=True) returns for its greedy
         `scores`; 0 at forced positions and behind a row's EOS.  It is computed on the device next to the arg-max (OMNI_OP_GREEDY_STEP
         p4).  hf's `scores` tuple itself (a [B, vocab] tensor per step) is NOT produced: `.scores` does not exist.  With
-        num_beams > 1 it is a ValueError — beam search returns `sequences_scores`."""
+        num_beams > 1 it is a ValueError — beam search returns `sequences_scores`.
+
+        Generation controls (greedy decoding; each None = not set, as in transformers): repetition_penalty (float > 0; applied once
+        to every token of the history, the decoder start token included), no_repeat_ngram_size (int >= 0, 0 = off; None = the
+        checkpoint's), min_new_tokens (0..max_new_tokens: no EOS before), suppress_tokens, begin_suppress_tokens (first generated
+        position; the second one behind a forced BOS, as in transformers), bad_words_ids (up to 64 sequences of 2..8 tokens, any
+        number of single tokens).  They are transformers' processors of the same names in transformers' order, applied on the
+        device by OMNI_OP_GREEDY_CTRL_STEP: token ids equal transformers' on the CPU, and `token_logprobs` are those of the
+        processed scores.  The block of values is uploaded per call; every setting replays the same plan and graph, and a call
+        without controls (or with neutral ones: penalty 1.0, min_new_tokens 0, empty lists) runs the plans it always ran.
+        ValueError before anything reaches the device: a value outside its range, a token id outside the vocabulary, the EOS /
+        forced BOS / forced EOS token in suppress_tokens, begin_suppress_tokens or as a single-token bad word, and any non-neutral
+        control together with num_beams > 1.  Not supported: min_length, sequence_bias, the encoder-side processors,
+        prefix_allowed_tokens_fn, sampling.
+
+        Any OTHER keyword argument (**kw) is accepted and IGNORED, as it always was: transformers callers pass use_cache,
+        output_attentions and the like, which change nothing here.
+        """
         if do_sample:
             raise NotImplementedError("sampling is not implemented (greedy or beam search decoding)")
         output_scores = kw.pop("output_scores", False)
@@ -1362,6 +1565,9 @@ class Florence2Captioner:
         if output_scores and beam:
             raise ValueError("output_scores=True is a greedy-decoding output (num_beams=1); beam search returns sequences_scores")
         self.check_max_new(max_new_tokens, beam)
+        controls = self.generation_controls(dict(zip(GEN_CTRL_KEYS, (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
+                                                                     suppress_tokens, begin_suppress_tokens, bad_words_ids))),
+                                            max_new_tokens, beam)
         k = beam[0] if beam else 1
         if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= k:
             raise ValueError(f"num_return_sequences must be in 1..num_beams ({k}), got {num_return_sequences!r}")
@@ -1372,28 +1578,33 @@ class Florence2Captioner:
 
             def fill(cp, s, n):
                 cp.x_in.t[:n, :, :, :3] = pixel_values[s:s + n].to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
-            parts = self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill, prompt, output_scores)
+            parts = self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill, prompt, output_scores, controls)
             if output_scores:
                 seq, logp = self._results_scores(parts)
                 return SimpleNamespace(sequences=seq, sequences_scores=None, token_logprobs=logp)
             seq, scores = self._results(parts, beam, num_return_sequences)
         return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
 
-    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False):
+    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False, controls=None):
         """encode + decode n_all images in chunks of `chunk` on the captioner's stream, each on the plan of its bucket: fill(cp, s, n)
         writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  prompt: `prompt_batch`
         of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results` (scores: plans that
-        also return the token log-probabilities, for `_results_scores`)."""
+        also return the token log-probabilities, for `_results_scores`).  controls: non-neutral `GenerationControls` (None = the
+        plans without them): every chunk runs on a controls plan, its block uploaded on the stream before the first step."""
         n_txt = prompt[2] if prompt else None
+        block = controls.pack(self.w.vocab, self.w.forced_bos) if controls else None
         chunk = min(chunk, self.long_plan_rows(max_new_tokens, beam[0] if beam else 1))     # 128 up to T = 227: as before
         if src.is_cuda:                                     # pixels / a screenshot the caller is still producing on its own stream
             self.stream.wait_stream(torch.cuda.current_stream(src.device))
         parts = []
         for s in range(0, n_all, chunk):
             n = min(chunk, n_all - s)
-            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam, n_txt=n_txt, **({"scores": True} if scores else {}))
+            cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam, n_txt=n_txt, **({"scores": True} if scores else {}),
+                            **({"controls": True} if controls else {}))
             with torch.cuda.stream(self.stream):
                 cp.reset()
+                if controls:
+                    cp.set_controls(block)
                 fill(cp, s, n)
                 if prompt:
                     cp.set_prompt(prompt[0][s:s + n].to(self.device, non_blocking=True), prompt[1][s:s + n].to(self.device, non_blocking=True), n)
@@ -1429,14 +1640,16 @@ class Florence2Captioner:
 
     @torch.inference_mode()
     def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None,
-                      prompt_ids=None, return_scores=None):
+                      prompt_ids=None, return_scores=None, controls=None):
         """Fused fast path: crops are cut, resized (cv2-bilinear 64x64, then Pillow-bicubic to R on the
         768 path) and normalised on device from the HBM-resident screenshot (ref:util/utils.py:97-123).
         num_beams: None = `self.num_beams` (default 1, greedy); k > 1 = beam search, the best hypothesis per crop (what
         generate(num_beams=k) returns for the same pixels).
         prompt_ids: one list of token ids (bos ... eos) for all crops, None = the default PROMPT_IDS; see `prompt_batch`.
         return_scores: None = `self.token_scores` (default False); True returns (ids, token_logprobs) — f32 [n, ids.shape[1] - 1],
-        aligned with ids[:, 1:], see `generate(output_scores=True)` and `caption_confidence`; greedy decoding only."""
+        aligned with ids[:, 1:], see `generate(output_scores=True)` and `caption_confidence`; greedy decoding only.
+        controls: a `GenerationControls` or a dict of its keys (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
+        suppress_tokens, begin_suppress_tokens, bad_words_ids), see `generate`; None or neutral = the call as it was."""
         beam = self.beam_config(num_beams)
         scores = self.token_scores if return_scores is None else return_scores
         if not isinstance(scores, bool):
@@ -1444,6 +1657,7 @@ class Florence2Captioner:
         if scores and beam:
             raise ValueError("token scores are a greedy-decoding output (num_beams=1); beam search has none")
         self.check_max_new(max_new_tokens, beam)
+        controls = self.generation_controls(controls, max_new_tokens, beam)
         prompt = self.prompt_batch([list(prompt_ids)] * len(boxes_px), self.resolution) if prompt_ids is not None and len(boxes_px) else None
         batch_size = max(1, min(int(batch_size), 128))      # plan capacity: buckets stop at 128 crops (the reference's default batch)
 
@@ -1451,7 +1665,7 @@ class Florence2Captioner:
             rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
             self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
         with self._lock:
-            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt, scores)
+            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt, scores, controls)
         if not parts:
             ids = torch.zeros((0, 1), dtype=torch.long)
             return (ids, torch.zeros((0, 0), dtype=torch.float32)) if scores else ids

@@ -9,7 +9,7 @@ Slot meanings: include/omni_amd.h."""
 NAMES = {1: "conv_igemm/conv_split", 2: "avgpool2", 3: "maxpool", 4: "resize_nearest", 5: "letterbox", 6: "detect_decode", 7: "nms",
          8: "dwconv3", 9: "layernorm", 10: "attn_rows (window / MHA)", 11: "chan_attn", 12: "proj_prep", 13: "assemble", 14: "embed_step",
          15: "attn_decode", 16: "greedy_step", 17: "crop_resize", 18: "dwconv3_ln", 19: "split_convert", 20: "hand_off", 21: "overlay",
-         22: "png_pack", 23: "png_deflate", 24: "mlp_fused"}
+         22: "png_pack", 23: "png_deflate", 24: "mlp_fused", 26: "greedy_ctrl_step"}
 
 MFMA_KINDS = (1, 24, 10)          # priced against the dense f16 MFMA peak; everything else against HBM
 
@@ -47,7 +47,7 @@ def op_work(op, esz=4):
     if k == 15:
         B, heads, nk = i[10], i[6], (i[7] if i[7] > 0 else i[8])
         return 4 * B * heads * nk * 64, esz * B * nk * i[9] * 2
-    if k == 16:
+    if k in (16, 26):
         return 0, esz * i[0] * i[1]
     return 0, 0
 

@@ -13,6 +13,7 @@ unchanged — plus what a GPU service needs and the reference lacks (SURVEY §8(
   per image (never stored on the shared parser — requests are concurrent).
 """
 import argparse
+import json
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -161,6 +162,9 @@ def main():
     ap.add_argument("--BOX_TRESHOLD", type=float, default=0.05)
     ap.add_argument("--caption_confidence", action="store_true",
                     help="captioned icons of parsed_content_list gain \"confidence\" (geometric-mean probability of the greedy tokens)")
+    ap.add_argument("--caption_generation", type=json.loads, default=None,
+                    help="generation controls of the captions as a JSON object, e.g. '{\"repetition_penalty\": 1.3, \"min_new_tokens\": 4}' "
+                         "(keys: repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, bad_words_ids)")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
     a = ap.parse_args()

@@ -72,6 +72,17 @@ class Omniparser(object):
             if isinstance(mn, bool) or not isinstance(mn, int) or mn < 1:
                 raise ValueError(f"caption_max_new_tokens must be an integer >= 1, got {mn!r}")
             self.caption_max_new_tokens = mn
+        # caption_generation: a dict of generation controls for the icon captions and `describe` (repetition_penalty,
+        # no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, bad_words_ids — Florence2Captioner.generate);
+        # None (default) = the calls as they were.  Types and limits are checked here, ids against the vocabulary by the captioner.
+        self.caption_generation = None
+        if config.get("caption_generation") is not None:
+            from ..florence import GenerationControls
+            cg = config["caption_generation"]
+            if not isinstance(cg, dict):
+                raise ValueError(f"caption_generation must be a dict of generation controls or None, got {cg!r}")
+            GenerationControls.of(cg)
+            self.caption_generation = dict(cg)
 
     def _ocr(self, image: Image.Image, ocr=None):
         """`ocr` = (texts, xyxy px boxes) handed over by the caller for THIS image; else the configured provider."""
@@ -84,13 +95,17 @@ class Omniparser(object):
         labeled, _coords, elements = U.get_som_labeled_img(
             image, self.som_model, BOX_TRESHOLD=self.config["BOX_TRESHOLD"], ocr_bbox=boxes, ocr_text=texts,
             draw_bbox_config=overlay_style(image.size), caption_model_processor=self.caption_model_processor, **_SOM_ARGS,
-            **({"max_new_tokens": self.caption_max_new_tokens} if self.caption_max_new_tokens != 20 else {}))
+            **({"max_new_tokens": self.caption_max_new_tokens} if self.caption_max_new_tokens != 20 else {}),
+            **({"generation": self.caption_generation} if self.caption_generation is not None else {}))
         return labeled, elements
 
-    def describe(self, image_base64: str, task="<MORE_DETAILED_CAPTION>", max_new_tokens=256):
+    def describe(self, image_base64: str, task="<MORE_DETAILED_CAPTION>", max_new_tokens=256, generation=None):
         """`utils.describe_image` of the whole screenshot: one description (or, with task="<OCR>", the text) from the caption model
-        alone — no detector, no OCR engine."""
-        return U.describe_image(decode_image(image_base64), self.caption_model_processor, task=task, max_new_tokens=max_new_tokens)
+        alone — no detector, no OCR engine.  generation: a dict of generation controls for this call; None = the configured
+        `caption_generation` (default: none)."""
+        generation = self.caption_generation if generation is None else generation
+        return U.describe_image(decode_image(image_base64), self.caption_model_processor, task=task, max_new_tokens=max_new_tokens,
+                                **({"generation": generation} if generation is not None else {}))
 
     def parse(self, image_base64: str, ocr=None):
         return self.parse_image(decode_image(image_base64), ocr)

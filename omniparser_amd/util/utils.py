@@ -404,7 +404,7 @@ def crop_boxes_px(ratio_boxes, W, H):
 
 @torch.inference_mode()
 def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_model_processor, prompt=None, batch_size=128,
-                            return_confidence=False, max_new_tokens=None):
+                            return_confidence=False, max_new_tokens=None, generation=None):
     """ref:util/utils.py:88-132.  Crops are cut/resized/normalised on device and captioned by the HIP
     captioner; `image_source` may be the uint8 HWC numpy image (as in the reference) or a device tensor.
     prompt: the caption prompt of every crop, as the reference's (a Florence-2 task token or free text,
@@ -412,7 +412,10 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
     return_confidence: (caption, confidence) pairs instead of captions — `florence.caption_confidence` of the greedy tokens'
     log-probabilities, which the captioner then computes next to its arg-max (`caption_crops(return_scores=True)`).
     max_new_tokens: tokens generated per crop; None = 20, the reference's call.  With a prompt that asks for more than a label
-    (`<DETAILED_CAPTION>`, free text) a larger value gives per-icon descriptions; the captioner validates it."""
+    (`<DETAILED_CAPTION>`, free text) a larger value gives per-icon descriptions; the captioner validates it.
+    generation: a dict of generation controls (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens,
+    begin_suppress_tokens, bad_words_ids; `Florence2Captioner.generate`) handed to `caption_crops(controls=...)`; None = the call
+    as it was."""
     model, processor = caption_model_processor["model"], caption_model_processor["processor"]
     max_new = 20 if max_new_tokens is None else max_new_tokens
     non_ocr = filtered_boxes[starting_idx:] if starting_idx else filtered_boxes
@@ -424,6 +427,8 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
     img_dev = img_dev.to(model.device)
     # prompt=None / "<CAPTION>": the call it always was (captioners without the keyword keep working); else the processor's ids
     pkw = {} if prompt is None or prompt == "<CAPTION>" else {"prompt_ids": processor.prompt_ids(prompt)}
+    if generation is not None:
+        pkw["controls"] = generation
     if return_confidence:                    # only when asked for: captioners without the keyword keep working
         from ..florence import caption_confidence
         ids, logp = model.caption_crops(img_dev, boxes_px, max_new_tokens=max_new, batch_size=batch_size, return_scores=True, **pkw)
@@ -435,19 +440,37 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
     return [t.strip() for t in texts]
 
 
+def _generation_kwargs(generation):
+    """`generation` (None, a dict of generation controls or a GenerationControls) as keyword arguments of `generate`"""
+    if generation is None:
+        return {}
+    if isinstance(generation, dict):
+        return dict(generation)
+    from ..florence import GEN_CTRL_KEYS
+    return {k: getattr(generation, k) for k in GEN_CTRL_KEYS}
+
+
 @torch.inference_mode()
-def describe_image(image_source, caption_model_processor, task="<MORE_DETAILED_CAPTION>", max_new_tokens=256, return_ids=False):
+def describe_image(image_source, caption_model_processor, task="<MORE_DETAILED_CAPTION>", max_new_tokens=256, return_ids=False,
+                   generation=None):
     """Describe or read ONE WHOLE image (no detector, no crops): the image is resized to the captioner's resolution with Pillow
     bicubic — the processor's own resize at 768 — normalised by the processor, and decoded greedily from the task prompt; the text
     is `batch_decode` of the ids, stripped.  image_source: a path, a PIL image or an HWC uint8 array; a list of them gives a list
     of strings.  task: a Florence-2 task token without an input (`<CAPTION>`, `<DETAILED_CAPTION>`, `<MORE_DETAILED_CAPTION>`,
     `<OCR>`, ...) or free text, under the rules of `FlorenceProcessor.prompt_ids`: everything but `<CAPTION>` needs the
     tokenizer.json next to the checkpoint, tasks with an input are refused.  max_new_tokens: up to the decoder's position capacity
-    (1024 for Florence-2-base).  return_ids: (text, ids i64 [T]) per image instead of the text."""
+    (1024 for Florence-2-base).  return_ids: (text, ids i64 [T]) per image instead of the text.  generation: a dict of generation
+    controls passed to `Florence2Captioner.generate` as keyword arguments (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
+    suppress_tokens, begin_suppress_tokens, bad_words_ids) — long greedy outputs are where a repetition penalty matters; None = the
+    call as it was."""
     if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be an integer >= 1, got {max_new_tokens!r}")
     if task is not None and not isinstance(task, str):
         raise ValueError(f"task is a Florence-2 task token or a free-text prompt (got {type(task).__name__})")
+    if generation is not None:
+        from ..florence import GenerationControls
+        generation = dict(generation) if isinstance(generation, dict) else generation
+        GenerationControls.of(generation)                  # a bad key or value: ValueError before the image is touched
     model, processor = caption_model_processor["model"], caption_model_processor["processor"]
     many = isinstance(image_source, (list, tuple))
     R = int(model.resolution)
@@ -462,7 +485,7 @@ def describe_image(image_source, caption_model_processor, task="<MORE_DETAILED_C
         return []
     inputs = processor(images=images, text=task, return_tensors="pt", do_resize=False)
     ids = model.generate(input_ids=inputs["input_ids"], pixel_values=inputs["pixel_values"], attention_mask=inputs["attention_mask"],
-                         max_new_tokens=max_new_tokens, num_beams=1, do_sample=False)
+                         max_new_tokens=max_new_tokens, num_beams=1, do_sample=False, **(_generation_kwargs(generation)))
     texts = [t.strip() for t in processor.batch_decode(ids, skip_special_tokens=True)]
     out = [(t, r) for t, r in zip(texts, ids)] if return_ids else texts
     return out if many else out[0]
@@ -704,11 +727,12 @@ def annotate_encode_device_batch(frames, boxes_per_frame, phrases_per_frame, **k
 def get_som_labeled_img(image_source: Union[str, Image.Image], model=None, BOX_TRESHOLD=0.01, output_coord_in_ratio=False,
                         ocr_bbox=None, text_scale=0.4, text_padding=5, draw_bbox_config=None, caption_model_processor=None,
                         ocr_text=[], use_local_semantics=True, iou_threshold=0.9, prompt=None, scale_img=False, imgsz=None,
-                        batch_size=128, caption_confidence=False, max_new_tokens=None):
+                        batch_size=128, caption_confidence=False, max_new_tokens=None, generation=None):
     """ref:util/utils.py:417-496 — returns (base64 PNG, label_coordinates, filtered_boxes_elem).
     caption_confidence (or a caption model with `token_scores` set): every element whose content the captioner wrote gains
     "confidence", see `florence.caption_confidence`; OCR elements and icons that took OCR text have no such key.
-    max_new_tokens: tokens generated per captioned icon, None = 20 (`get_parsed_content_icon`)."""
+    max_new_tokens: tokens generated per captioned icon, None = 20 (`get_parsed_content_icon`).
+    generation: generation controls of the icon captions, None = none (`get_parsed_content_icon`)."""
     if isinstance(image_source, str):
         image_source = Image.open(image_source)
     image_source = image_source.convert("RGB")
@@ -738,7 +762,8 @@ def get_som_labeled_img(image_source: Union[str, Image.Image], model=None, BOX_T
         conf = bool(caption_confidence or getattr(caption_model_processor["model"], "token_scores", False))
         parsed = get_parsed_content_icon(filtered_boxes, starting_idx, image_np, caption_model_processor, prompt=prompt,
                                          batch_size=batch_size, **({"return_confidence": True} if conf else {}),
-                                         **({"max_new_tokens": max_new_tokens} if max_new_tokens is not None else {}))
+                                         **({"max_new_tokens": max_new_tokens} if max_new_tokens is not None else {}),
+                                         **({"generation": generation} if generation is not None else {}))
         for box in elems:
             if box["content"] is None and parsed:
                 if conf:
