@@ -92,6 +92,15 @@ enum {
    *           format-B matrix of its own with its own power of two: p6 = f32[M / n] of 2^-k, read in place of f1 (NULL = f1 for all).
    *           n must be a multiple of the row tile the launcher takes (256, or 128 for short token matrices / OMNI_GEMM_TILE=128x128),
    *           else OMNI_E_ARG: the image of a tile is then uniform.  Written by OMNI_OP_CHAN_ATTN's fold mode (i8 = 1)
+   *  i28 = 1 (i20 = 2 only, additive; 0 = the epilogues above): SCORES EPILOGUE for the q|k launch of a folded channel block.  The weight
+   *           rows (and the bias) are ordered [q_0 | k_0 | q_1 | k_1 | ...], 32 rows per part, so that columns [64 g, 64 g + 64) of the
+   *           product are q and k of channel group g.  Nothing is written to p4 (it may be NULL and is not touched); every 256-row tile
+   *           is reduced to S[i][j] = sum_n q_g[n][i] k_g[n][j] over its rows (exact f32 products on the matrix pipe, in the summation
+   *           order of OMNI_OP_CHAN_ATTN at i5 = 256, bit for bit) and stored to p7 = f32[M / 256 * Cout / 64 * 1024] at
+   *           ((b * G + g) * chunks + chunk) * 1024 + i * 32 + j with G = Cout / 64, i26 = rows per image (> 0, % 256 == 0, M % i26 == 0;
+   *           i27 = 0 and p6 = NULL keep the one weight matrix), b = row / i26, chunks = i26 / 256: the workspace layout of
+   *           OMNI_OP_CHAN_ATTN, which then runs with i9 = 1.  Forces the 256x256 tile; needs Cout % 256 == 0, no activation, no residual,
+   *           i21 = 0 and a non-NULL p7, else OMNI_E_ARG
    *  i22 (i20 = 0 or 1; 0 = the launcher's heuristic): output tile (1 = 64x64, 2 = 128x64, 3 = 128x128).  With i20 = 0 the K-slice
    *           width and the split-K count still follow from the tile as they do unforced (128-row tiles walk 64-byte slices)
    *  i23 (i20 = 1 only, ignored otherwise; 0 = the heuristic): split-K count (1 = no split, no reduce launch).  i22 / i23 are the
@@ -172,7 +181,13 @@ enum {
    *  apply pass: p1 Wp f32[C, C] (plain), p2 W' f32[B, C, C] (one fma chain per element, i ascending), p3 the same as format-B
    *  matrices [B][C][C] of 4 bytes per element with W' 2^k = hi + lo, k per image such that the largest |W' 2^k| lies in [2^12, 2^13)
    *  (clamped to +-24; 0 for a zero matrix), p6 f32[B] = 2^-k, p7 f32[B * (C / 64) * G] scratch (block maxima).  p4 is not written and
-   *  may be NULL; q and k are read from p0 as f32, v is not read.  p3 / p6 feed OMNI_OP_CONV i26 / i27 / p6 */
+   *  may be NULL; q and k are read from p0 as f32, v is not read.  p3 / p6 feed OMNI_OP_CONV i26 / i27 / p6
+   *  i9 = 1 (additive; f32 plans, i5 % 8 == 0): p5 ALREADY HOLDS THE PARTIALS [B][G][chunks][32][32] (written by OMNI_OP_CONV i28 = 1 with
+   *  i5 = 256): the scores launch is skipped, p0 is not read; softmax (partials summed per element in ascending chunk order) and what
+   *  follows run as always
+   *  i10 = t > 0 (additive; f32 plans, t % 8 == 0, i5 % t == 0; 0 = i5): TOKENS PER PARTIAL.  Every chunk of i5 tokens is kept as i5 / t
+   *  partials of t tokens: chunks = ceil(N / t) in the layout of p5, in the scores launch and in the softmax's sum — the op at i5 = t, bit
+   *  for bit.  The captioner's folded stages run i5 = 1024, i10 = 256 (the row tile of OMNI_OP_CONV i28 = 1) */
   OMNI_OP_CHAN_ATTN = 11,
   /* projector input (florence2 :568-590): y[b] = [mean_n(x+pos+t) ; x+pos+t]; p0 x [B,N,C] p1 pos2d f32[N,C] p2 temporal f32[C] p4 y [B,N+1,C]
    *  i0 B i1 N i3 C */

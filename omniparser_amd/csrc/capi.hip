@@ -116,11 +116,15 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
         ext[1] += (nimg - 1) * (long long)i[27];
         ext[6] = nimg * 4;
       }
+      if (i[20] == 2 && i[28] == 1) {                        // scores epilogue: p7 = one 4 KB partial per 256-row chunk and 64-column group, no y
+        ext[7] = (M / 256) * (Cout / 64) * 4096;
+        ext[4] = 1;
+      }
       break;
     }
     case OMNI_OP_CHAN_ATTN: {
       // p0 qkv [B*N,3C] p4 o [B*N,C] p5 ws; fold mode (i8 = 1): p1 Wp f32[C,C] p2 W' f32[B,C,C] p3 W' format B p6 2^-k f32[B] p7 block maxima
-      const long long B = i[0], N = i[1], C = i[3], G = i[4], ct = i[5] > 0 ? i[5] : 1;
+      const long long B = i[0], N = i[1], C = i[3], G = i[4], ct = i[10] > 0 ? i[10] : (i[5] > 0 ? i[5] : 1);   // i10: tokens per partial
       ext[0] = B * N * 3 * C * esz; ext[4] = B * N * C * esz; ext[5] = B * G * ((N + ct - 1) / ct) * 1024 * 4;
       if (i[8] == 1) { ext[1] = C * C * 4; ext[2] = ext[3] = B * C * C * 4; ext[6] = B * 4; ext[7] = B * (C / 64) * G * 4; }
       break;

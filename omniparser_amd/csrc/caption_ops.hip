@@ -1558,11 +1558,25 @@ __global__ __launch_bounds__(256) void chan_softmax_kernel(ChanArgs a) {
   float* p0 = a.ws + ((long long)b * a.G + g) * a.chunks * 1024;
   const int i = threadIdx.x >> 3, j0 = (threadIdx.x & 7) * 4;
   {
+    // one add chain per element, ascending chunk; the loads do not depend on it, so eight chunks' 16-byte loads are issued before their
+    // adds (256-token chunks: 144 partials per element in DaViT stage 0) — the same sums in the same order
     const float* p = p0 + i * 32 + j0;
     float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < a.chunks; ++c)
+    int c = 0;
+    for (; c + 8 <= a.chunks; c += 8) {
+      f32x4 v[8];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += p[(long long)c * 1024 + e];
+      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4*>(p + (long long)(c + u) * 1024);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] += v[u][e];
+    }
+    for (; c < a.chunks; ++c) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(p + (long long)c * 1024);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] += v[e];
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e) sa[i][j0 + e] = s[e] * a.scale;
   }
@@ -2937,12 +2951,23 @@ static int launch_chan_attn(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE(!fold || (op->dtype == OMNI_F32 && a.chunk_tokens % 8 == 0 && a.C % 64 == 0 && op->p[1] && op->p[2] && op->p[3] && op->p[6] && op->p[7]),
                "chan_attn: fold mode needs an f32 plan, C %% 64 == 0, chunk_tokens %% 8 == 0 and p1 / p2 / p3 / p6 / p7");
   OMNI_REQUIRE(!a.osplit || op->dtype == OMNI_F32, "chan_attn: split output needs an f32 plan");
+  // i9 = 1: the workspace already holds the score partials (written by the scores epilogue of the q|k GEMM, OMNI_OP_CONV i28): no scores launch
+  const bool have_scores = op->i[9] == 1;
+  // i10 > 0: tokens per score partial where the partials are finer than the chunk i5 (the row tile of the q|k GEMM's scores epilogue):
+  // every chunk is kept as i5 / i10 partials, the workspace and the softmax's sum run over N / i10 of them — the op at i5 = i10
+  if (op->i[10] != 0) {
+    OMNI_REQUIRE(op->i[10] > 0 && op->i[10] % 8 == 0 && a.chunk_tokens % op->i[10] == 0 && op->dtype == OMNI_F32 && a.C % 4 == 0,
+                 "chan_attn: i10 = %d (tokens per partial) needs an f32 plan, i10 %% 8 == 0 and i5 %% i10 == 0", op->i[10]);
+    a.chunk_tokens = op->i[10];
+  }
+  OMNI_REQUIRE(op->i[9] == 0 || (have_scores && op->dtype == OMNI_F32 && a.chunk_tokens % 8 == 0 && a.C % 4 == 0),
+               "chan_attn: i9 = %d (partials already in the workspace) needs an f32 plan and chunk_tokens %% 8 == 0", op->i[9]);
   a.chunks = (a.N + a.chunk_tokens - 1) / a.chunk_tokens;
   a.scale = 1.0f / sqrtf((float)a.N);
   if (op->f[0] != 0.0f) a.scale = op->f[0];
   dim3 g1(a.chunks, a.G, a.B), g2((a.N + 255) / 256, a.G, a.B);
   if (op->dtype == OMNI_F32 && a.chunk_tokens % 8 == 0 && a.C % 4 == 0) {
-    hipLaunchKernelGGL(chan_scores_mfma_kernel, g1, dim3(256), 0, s, a);
+    if (!have_scores) hipLaunchKernelGGL(chan_scores_mfma_kernel, g1, dim3(256), 0, s, a);
     hipLaunchKernelGGL(chan_softmax_kernel, dim3(a.G, a.B), dim3(256), 0, s, a);
     if (fold) {
       FoldArgs f{};

@@ -42,7 +42,13 @@ struct GemmArgs {
   // image mt / img_tiles, whose weight matrix lies img * w_img_stride bytes behind w and whose 2^-k is img_oscale[img].
   // img_tiles == 0: one weight matrix and `oscale` for all rows
   int img_tiles; unsigned w_img_stride; const float* img_oscale;
+  // scores epilogue (GEMM_EPI_SCORES below): no output matrix — `y` is the channel-attention workspace f32 [image][group][chunk][32][32]
+  // and img_tiles the chunks per image (the struct, part of MlpArgs too, keeps its layout)
 };
+
+// One more value of the kernels' ACT parameter, outside the public OMNI_ACT_* range: no activation and no y at all — the tile's q|k values
+// are reduced to channel-attention score partials inside the epilogue (gemm_scores_epilogue below; 256x256 tile only).
+constexpr int GEMM_EPI_SCORES = 3;
 
 // 16-byte row accesses of an epilogue through a buffer descriptor that ends with the last valid row of the tile: the hardware's range
 // check drops a store (and zeroes a load) of a row at or beyond M, in place of a row compare, an exec mask update and 64-bit address
@@ -157,6 +163,81 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
     }
   }
   if constexpr (OSPLIT) omni_report_range(amax);
+}
+
+// Scores epilogue (OMNI_OP_CONV i28 = 1): the q|k launch of a folded channel block exists for the 32x32 score matrix per (image, group)
+// only, so its tile never goes to HBM.  The planner orders the weight rows [q_0 | k_0 | q_1 | k_1 | ...] (32 rows each): the 64 channels
+// of wave (wm, wn) are q and k of ONE group g = n0 / 64 + wn for the wave's 128 tokens.  Per 32-token tile the register stage of
+// gemm_epilogue (acc * 2^-k + bias in one fma, f32 rows into the wave's staging slice) is followed by 16 steps of v_mfma_f32_32x32x2_f32
+// that read the slice back in the operand mapping of caption_ops.hip::chan_scores_mfma_kernel — step u: lane (i, t) supplies q[2u + t][i]
+// as the row operand and k[2u + t][i] as the column operand.  The summation order is that kernel's at chunk_tokens = 256, bit for bit: its
+// wave w sums tokens [64 w, 64 w + 64) of the chunk in ascending order into one accumulator = here r0, r1 (token tiles 0-1, 2-3 of the
+// wm = 0 wave) and r2, r3 (wm = 1), combined as ((r0 + r1) + r2) + r3.  The wm = 1 waves hand their two matrices over through the LDS
+// ring behind the staging slices (one block-wide barrier), the wm = 0 waves write the 4 KB partial of their group in the D layout.
+template <int BM, int BN, int WM, int WN, int TM, int TN, int LDS_BYTES>
+__device__ __forceinline__ void gemm_scores_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& a, unsigned char* lds, int img, int chunk, int n0, int wave,
+                                                     int lane, float osc) {
+  static_assert(BM == 256 && BN == 256 && WM == 2 && WN == 4 && TM == 4 && TN == 2, "scores epilogue: 256x256 tile, a wave owns 128 tokens x 64 channels");
+  constexpr int NW = WM * WN, EP = 272, HAND = NW * 32 * EP;   // staged row pitch as in gemm_epilogue; hand-over area behind the slices
+  static_assert(HAND + WN * 2 * 4096 <= LDS_BYTES, "hand-over matrices must fit the LDS ring behind the staging slices");
+  const int wm = wave / WN, wn = wave % WN;
+  const int hsel = lane >> 5;
+  __syncthreads();                                           // every wave is done reading the last K slice
+  unsigned char* stg = lds + wave * (32 * EP);
+  const int nw0 = n0 + wn * 64;                              // first channel of this wave: q of its group, k 32 further
+  f32x4 bq[2][4];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      bq[j][q] = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + nw0 + 4 * hsel + j * 32 + q * 8) : f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x16 sc[2];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) { sc[0][e] = 0.0f; sc[1][e] = 0.0f; }
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    unsigned char* wr = stg + (lane & 31) * EP;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x16& ac = acc[i][j];
+        float v[4];
+#pragma unroll
+        for (int c = 0; c < 4; c += 2) {
+          const f32x2 t = __builtin_elementwise_fma(f32x2{ac[q * 4 + c], ac[q * 4 + c + 1]}, (f32x2)osc, f32x2{bq[j][q][c], bq[j][q][c + 1]});
+          v[c] = t[0]; v[c + 1] = t[1];
+        }
+        *reinterpret_cast<f32x4*>(wr + (j * 32 + q * 8 + 4 * hsel) * 4) = f32x4{v[0], v[1], v[2], v[3]};
+      }
+    OMNI_WAVE_SYNC();
+    const unsigned char* rd = stg + hsel * EP + (lane & 31) * 4;   // token 2u + (lane >> 5) of the tile, channel lane & 31 of q (k: +128 bytes)
+    float qv[16], kv[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      qv[u] = *reinterpret_cast<const float*>(rd + 2 * u * EP);
+      kv[u] = *reinterpret_cast<const float*>(rd + 2 * u * EP + 128);
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) sc[i >> 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qv[u], kv[u], sc[i >> 1], 0, 0, 0);
+    OMNI_WAVE_SYNC();                                        // the next token tile overwrites the staging rows
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  float* hand = reinterpret_cast<float*>(lds + HAND) + wn * 2048;   // [2 matrices][16 accumulator registers][64 lanes] of column wn
+  if (wm == 1) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) hand[(r * 16 + e) * 64 + lane] = sc[r][e];
+  }
+  __syncthreads();                                           // all eight waves: the wm = 1 matrices are published
+  if (wm == 0) {
+    // D layout: col j = lane & 31, row i = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+    float* out = reinterpret_cast<float*>(a.y) + ((((long long)img * (a.N / 64) + (n0 / 64 + wn)) * a.img_tiles + chunk) * 1024 + (lane & 31));
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      out[((e & 3) + 8 * (e >> 2) + 4 * hsel) * 32] = ((sc[0][e] + sc[1][e]) + hand[e * 64 + lane]) + hand[(16 + e) * 64 + lane];
+  }
 }
 
 // K-loop schedule: the DMA pieces of the slice NSTAGE-1 ahead are spread over the units, ds_reads / DMA pieces interleaved one per
@@ -415,7 +496,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_dma_kernel(GemmArgs a) {
   }
 
   // ---- epilogue (gemm_epilogue above): bias / activation / 2^-k in registers, rows transposed through the idle LDS ring
-  gemm_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE, ACT, OSPLIT, RES>(acc, a, lds, m0, n0, wave, lane, osc);
+  if constexpr (ACT == GEMM_EPI_SCORES)
+    gemm_scores_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE>(acc, a, lds, img, __builtin_amdgcn_readfirstlane(mt) - img * a.img_tiles, n0, wave, lane, osc);
+  else
+    gemm_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE, ACT, OSPLIT, RES>(acc, a, lds, m0, n0, wave, lane, osc);
 #endif
 }
 
@@ -605,7 +689,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_kernel(MlpArgs a) {
 }
 
 template <int BM, int BN, int WM, int WN, int NSTAGE>
-int launch_tile(GemmArgs& a, int rows_per_img, int act, int osplit, hipStream_t s) {
+int launch_tile(GemmArgs& a, int rows_per_img, int act, int osplit, bool scores, hipStream_t s) {
   if (rows_per_img % BM != 0) {
     omni_set_error("gemm_dma: per-image weights need whole %d-row tiles per image (rows per image %d)", BM, rows_per_img);
     return OMNI_E_ARG;
@@ -632,7 +716,11 @@ int launch_tile(GemmArgs& a, int rows_per_img, int act, int osplit, hipStream_t 
     }                                                                                                                              \
     hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, NSTAGE, ACT_, OS_, RES_, SCHED1>), grid, block, 0, s, a);                  \
   } while (0)
-  if (act == OMNI_ACT_NONE && !osplit && !res) OMNI_GD(OMNI_ACT_NONE, false, false);
+  if (scores) {
+    if constexpr (BM == 256 && BN == 256) OMNI_GD(GEMM_EPI_SCORES, false, false);
+    else { omni_set_error("gemm_dma: the scores epilogue is built for the 256x256 tile"); return OMNI_E_ARG; }
+  }
+  else if (act == OMNI_ACT_NONE && !osplit && !res) OMNI_GD(OMNI_ACT_NONE, false, false);
   else if (act == OMNI_ACT_NONE && !osplit && res) OMNI_GD(OMNI_ACT_NONE, false, true);
   else if (act == OMNI_ACT_NONE && osplit && !res) OMNI_GD(OMNI_ACT_NONE, true, false);
   else if (act == OMNI_ACT_GELU && osplit && !res) OMNI_GD(OMNI_ACT_GELU, true, false);
@@ -660,7 +748,11 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
   const int osplit = op->i[21];
   a.oscale = op->f[1] != 0.0f ? op->f[1] : 1.0f;
   OMNI_REQUIRE(op->dtype == OMNI_F32, "gemm_dma: f32 plans only");
-  OMNI_REQUIRE(a.x && a.w && a.y, "gemm_dma: null pointer");
+  // scores epilogue (i28 = 1, p7 = ws): no y — the tile's q|k values end as channel-attention partials (gemm_scores_epilogue)
+  OMNI_REQUIRE(op->i[28] == 0 || op->i[28] == 1, "gemm_dma: unknown epilogue mode %d (i28)", op->i[28]);
+  const bool scores = op->i[28] == 1;
+  OMNI_REQUIRE(a.x && a.w && (a.y || scores), "gemm_dma: null pointer");
+  if (scores) a.y = (unsigned char*)op->p[7];                // p4 is not touched: the kernel's only output is the workspace
   OMNI_REQUIRE(op->i[6] == 1 && op->i[7] == 1 && op->i[8] == 1 && op->i[9] == 0 && op->i[10] == H && op->i[11] == W,
                "gemm_dma: pointwise layers only");
   OMNI_REQUIRE(op->f[0] == 0.0f, "gemm_dma: output scale is not supported");
@@ -683,6 +775,12 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
     a.w_img_stride = (unsigned)op->i[27];
     a.img_oscale = (const float*)op->p[6];
   }
+  if (scores) {
+    OMNI_REQUIRE(a.y, "gemm_dma: the scores epilogue needs its workspace (p7)");
+    OMNI_REQUIRE(rows_per_img > 0 && rows_per_img % 256 == 0, "gemm_dma: the scores epilogue needs whole 256-row chunks per image (i26 = %d)", rows_per_img);
+    OMNI_REQUIRE(a.N % 256 == 0, "gemm_dma: the scores epilogue needs N %% 256 == 0 (N %d)", a.N);
+    OMNI_REQUIRE(act == OMNI_ACT_NONE && !a.res && !osplit, "gemm_dma: the scores epilogue takes no activation, residual or format-B output");
+  }
   // tile choice: 256x256 (one 8-wave block per CU, 128x64 per wave) when N allows, 256x128 otherwise — as long as the launch
   // still has a block for every CU; a short token matrix (small caption batches, 64x64 crops) takes 128x128 tiles instead, which
   // quarter the padded rows and give the chip 4x the blocks.  OMNI_GEMM_TILE (256x256 | 256x128 | 128x128) is the A/B knob of
@@ -697,10 +795,11 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
     else if (!strcmp(e, "128x128")) tile = 2;
     else if (!strcmp(e, "256x256") && a.N % 256 == 0) tile = 0;
   }
+  if (scores) tile = 0;                                      // the mode forces the tile its epilogue is written for
   int rc;
-  if (tile == 0) rc = launch_tile<256, 256, 2, 4, 2>(a, rows_per_img, act, osplit, s);
-  else if (tile == 1) rc = launch_tile<256, 128, 4, 2, 3>(a, rows_per_img, act, osplit, s);
-  else rc = launch_tile<128, 128, 2, 2, 2>(a, rows_per_img, act, osplit, s);
+  if (tile == 0) rc = launch_tile<256, 256, 2, 4, 2>(a, rows_per_img, act, osplit, scores, s);
+  else if (tile == 1) rc = launch_tile<256, 128, 4, 2, 3>(a, rows_per_img, act, osplit, false, s);
+  else rc = launch_tile<128, 128, 2, 2, 2>(a, rows_per_img, act, osplit, false, s);
   if (rc) return rc;
   OMNI_HIP_CHECK(hipGetLastError());
   return OMNI_OK;

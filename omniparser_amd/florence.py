@@ -924,12 +924,17 @@ class _CaptionPlans(_StepPlans):
             # no [B, H, H, 4C] tensor (9.7 GB of a 128-crop plan at 768x768), 12 instead of 44 bytes of HBM traffic per token-channel
             mlp_one = grp["dma"] and cap.fuse_mlp and C == 128 and sd[f"{vt}blocks.{s}.0.spatial_block.ffn.fc1.weight"].shape[0] == 512
             ffn = None if mlp_one else pb.alloc(B, H, H, 4 * C)
-            chunk_tokens = 1024
-            chunks = (N + chunk_tokens - 1) // chunk_tokens
-            cws = pb.raw((B * w.groups[s] * chunks * 1024,), torch.float32, zero=False)
             # fold rule: the fold's bytes and MACs grow with C^2 per image, what it saves with N * C — worth it from N >= 4 C on;
             # whole 256-row GEMM tiles per image.  768x768 crops: stages 0-2; 64x64 crops: none
             fold = bool(cap.fold_chan_proj) and grp["dma"] and dt == L.F32 and C % 128 == 0 and N % 256 == 0 and N >= 4 * C
+            # folded stages keep their scores as 256-token partials — the row tile of the q|k GEMM, whose scores epilogue writes one partial
+            # per tile and group (cap.chan_scores_in_gemm) — on BOTH sides of that switch: the standalone scores kernel then gives the same
+            # bits.  The chunk (i5) stays 1024 in every stage; folded stages carry the partial size in OMNI_OP_CHAN_ATTN i10
+            chunk_tokens = 1024
+            partial_tokens = 256 if fold else 0
+            chunks = (N + (partial_tokens or chunk_tokens) - 1) // (partial_tokens or chunk_tokens)
+            cws = pb.raw((B * w.groups[s] * chunks * 1024,), torch.float32, zero=False)
+            scores_in_gemm = fold and bool(cap.chan_scores_in_gemm)
             fold_wf = fold_wb = fold_sc = fold_mx = None
             if fold:                                      # stage scratch, image-major: an exact-row twin uses the first n images' part
                 fold_wf = pb.raw((B * C * C,), torch.float32, zero=False)
@@ -964,7 +969,14 @@ class _CaptionPlans(_StepPlans):
                             pb.weight_rows(wp, 0, 2 * C), pb.upload(sd[key + ".bias"][:2 * C].float()),
                             pb.weight_rows(wp, 2 * C, C), pb.upload(sd[key + ".bias"][2 * C:].float())))
                         assert hbuf.fmt == "split"
-                        pb.conv(tokens(hbuf), wqk, bqk, tokens(qkv.slice(0, 2 * C)), 1)
+                        if scores_in_gemm:
+                            # nobody but the scores reads q|k: the launch reduces its tiles to the score partials in its epilogue (rows
+                            # ordered [q_g | k_g] per group) and the op below starts at the softmax — no q|k tensor, no scores kernel
+                            wqs, bqs = W.cached((key, dt, "dma-qk-groups"), lambda: (
+                                pb.pack_weight_qk_groups(wqk), pb.upload(sd[key + ".bias"][:2 * C].float()[pb.qk_group_rows(C)])))
+                            pb.conv_scores(tokens(hbuf), wqs, bqs, cws, N)
+                        else:
+                            pb.conv(tokens(hbuf), wqk, bqk, tokens(qkv.slice(0, 2 * C)), 1)
                         vs = tokens(qkv.slice(2 * C, C))
                         pb.conv(tokens(hbuf), wv, bv, vs, 1, out_split=True)
                         pkey = pre + "channel_attn.proj"
@@ -973,7 +985,8 @@ class _CaptionPlans(_StepPlans):
                         pb.add_op(L.make_op(L.OP_CHAN_ATTN, dt,
                                             p=[qkv.ptr, wplain.data_ptr(), fold_wf.data_ptr(), fold_wb.data_ptr(), None, cws.data_ptr(),
                                                fold_sc.data_ptr(), fold_mx.data_ptr()],
-                                            i={0: B, 1: N, 3: C, 4: w.groups[s], 5: chunk_tokens, 6: 1 if (attn_split and grp["dma"]) else 0, 8: 1}))
+                                            i={0: B, 1: N, 3: C, 4: w.groups[s], 5: chunk_tokens, 6: 1 if (attn_split and grp["dma"]) else 0, 8: 1,
+                                               9: 1 if scores_in_gemm else 0, 10: partial_tokens}))
                         pb.conv_per_image(vs, fold_wb, fold_sc, bproj, tokens(B_), tokens(B_), N)
                     else:
                         linear(pre + "channel_attn.qkv", hbuf, qkv)
@@ -1142,6 +1155,9 @@ class Florence2Captioner:
     attn_split_out = True     # attention kernels write format B for the projection GEMM themselves
     fold_chan_proj = True     # channel attention's apply pass folded into a per-image projection weight where N >= 4 C (f32 LDS-DMA plans;
                               # DaViT stages 0-2 at 768x768, nothing at 64x64): OMNI_OP_CHAN_ATTN i8 = 1 + OMNI_OP_CONV i26 / i27 / p6
+    chan_scores_in_gemm = True   # folded stages: the q|k launch reduces its tiles to the score partials in its epilogue (OMNI_OP_CONV i28 / p7)
+                              # and OMNI_OP_CHAN_ATTN starts at the softmax (i9 = 1); off: plain q|k launch + the standalone scores kernel
+                              # over the same 256-token chunks — bit-identical results (the A/B and test switch)
     fuse_mlp = True           # fc1 + GELU + fc2 + residual of the C = 128 stage as ONE kernel (OMNI_OP_MLP_FUSED): no hidden tensor in HBM
     exact_rows = os.environ.get("OMNI_EXACT_ROWS", "1") != "0"   # merged decode: the remainder micro-batch of a caption batch encodes exactly
                               # its own rows, as a second hipGraph over the buffers of the lane's full-capacity plan (`_CaptionPlans.encode_rows`),

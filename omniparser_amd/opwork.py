@@ -23,6 +23,8 @@ def op_work(op, esz=4):
         if i[25]:                                   # row-patch mode: algorithmic K = k x k taps x 4 stored channels (the op's 32 k holds zero weights)
             K = i[6] * i[6] * i[4]
             return 2 * M * N * K, esz * (i[0] * i[1] * i[2] * i[4] + N * K + M * N)
+        if i[20] == 2 and i[28] == 1:               # scores epilogue: no y, one 4 KB partial per 256-row chunk and 64-column group
+            return 2 * M * N * K + 2 * M * N * 16, esz * (M * K + N * K + (M // 256) * (N // 64) * 1024)
         nw = M // i[26] if (i[20] == 2 and i[26] > 0) else 1          # per-image weights: one matrix per image
         return 2 * M * N * K, esz * (i[0] * i[1] * i[2] * i[3] + nw * N * K + M * N * (2 if op.p[3] else 1))
     if k == 24:                                     # fc1 + GELU + fc2 + residual: h in, residual in, y out, both weight matrices
@@ -41,6 +43,10 @@ def op_work(op, esz=4):
         return 4 * groups * heads * nq * nk * D, esz * groups * (nq + 2 * nk + nq) * heads * D
     if k == 11:
         B, N, C = i[0], i[1], i[3]
+        if i[8] == 1 and i[9] == 1:                 # fold mode behind the scores epilogue: reads the partials instead of q and k
+            ct = i[10] or i[5]                      # tokens per partial
+            chunks = (N + ct - 1) // ct
+            return 2 * B * C * C * 32, esz * (B * (C // 32) * chunks * 1024 + C * C + B * C * C)
         if i[8] == 1:                               # fold mode: scores over q and k, then W'_b = Wp . blockdiag(A) written once per image
             return 2 * B * N * C * 32 + 2 * B * C * C * 32, esz * (B * N * C * 2 + C * C + B * C * C)
         return 4 * B * N * C * 32, esz * B * N * C * 4
@@ -66,7 +72,7 @@ def op_shape(op):
     if k == 10:
         return (i[11] * i[9], i[8] * i[15], i[12])
     if k == 11:
-        return (i[0] * i[1], i[3], 1 if i[8] == 1 else 0)
+        return (i[0] * i[1], i[3], (2 if i[9] == 1 else 1) if i[8] == 1 else 0)
     if k == 15:
         return (i[10], i[9], i[7] if i[7] > 0 else i[8])
     return (i[0], i[3], 0)
@@ -75,9 +81,11 @@ def op_shape(op):
 def op_kernel(op):
     """the kernel family a launch of this op runs (kind 1 is served by three kernels, chosen by the planner: slot i20)."""
     if op.kind == 1:
+        if op.i[20] == 2 and op.i[28] == 1:
+            return "gemm_dma (scores epilogue)"
         if op.i[20] == 2 and op.i[26] > 0:
             return "gemm_dma (per-image weights)"
         return "gemm_dma" if op.i[20] == 2 else ("conv_split" if op.i[20] else "conv_igemm")
     if op.kind == 11 and op.i[8] == 1:
-        return "chan_attn (scores + fold)"
+        return "chan_attn (fold)" if op.i[9] == 1 else "chan_attn (scores + fold)"
     return NAMES.get(op.kind, str(op.kind))

@@ -363,6 +363,44 @@ class PlanBuilder:
         self.bytes += 4 * (M * K + nimg * cout * K + M * cout * (2 if res is not None else 1))
         return out
 
+    @staticmethod
+    def qk_group_rows(C: int):
+        """row order [q_0 | k_0 | q_1 | k_1 | ...] (32 rows each) of a q|k weight [2C, K] whose rows are [q (C) | k (C)]: every 64-row span
+        holds q and k of ONE 32-channel group, which is what a wave of the scores epilogue owns"""
+        assert C % 32 == 0
+        return [part * C + g * 32 + r for g in range(C // 32) for part in (0, 1) for r in range(32)]
+
+    def pack_weight_qk_groups(self, w_qk: torch.Tensor) -> torch.Tensor:
+        """format-B q|k weight [2C rows] (rows of a pack_weight_dma matrix: same halves, same 2^-k) -> its rows in `qk_group_rows` order as
+        a weight of its own, for `conv_scores`.  The dot product of every row is unchanged, bit for bit."""
+        assert getattr(w_qk, "omni_fmt", 0) == 2 and w_qk.shape[0] % 64 == 0
+        idx = torch.tensor(self.qk_group_rows(w_qk.shape[0] // 2), device=w_qk.device)
+        t = self.upload(w_qk[idx])
+        t.omni_fmt, t.omni_oscale = 2, w_qk.omni_oscale
+        return t
+
+    def conv_scores(self, x: View, w_qk: torch.Tensor, bias: Optional[torch.Tensor], ws: torch.Tensor, rows_per_img: int):
+        """the q|k launch of a folded channel block with the SCORES EPILOGUE (OMNI_OP_CONV i20 = 2 with i28 = 1, p7; csrc/gemm_dma.hip
+        gemm_scores_epilogue): q|k = x . w_qk^T + bias is reduced inside the GEMM to the channel-attention partials
+        ws[image][group][256-token chunk][32][32] that OMNI_OP_CHAN_ATTN (i9 = 1) sums; nothing else is written.  `w_qk` and `bias` in
+        `qk_group_rows` order, image b = rows [b * rows_per_img, (b + 1) * rows_per_img) of x."""
+        cout, K = w_qk.shape[0], x.C
+        M = x.B * x.H * x.W
+        assert self.dtype == L.F32 and x.fmt == "split" and x.ld % 16 == 0 and x.coff % 16 == 0 and K % 32 == 0
+        assert getattr(w_qk, "omni_fmt", 0) == 2 and w_qk.numel() == 2 * cout * K and cout % 256 == 0
+        assert rows_per_img > 0 and rows_per_img % 256 == 0 and M % rows_per_img == 0
+        assert ws.dtype == torch.float32 and ws.numel() >= (M // 256) * (cout // 64) * 1024
+        assert bias is None or (bias.dtype == torch.float32 and bias.numel() == cout and bias.device.type == self.device.type)
+        self.ops.append(L.make_op(
+            L.OP_CONV, self.dtype,
+            p=[x.ptr, w_qk.data_ptr(), bias.data_ptr() if bias is not None else None, None, None, None, None, ws.data_ptr()],
+            i={0: x.B, 1: x.H, 2: x.W, 3: K, 4: x.ld, 5: x.coff, 6: 1, 7: 1, 8: 1, 9: 0, 10: x.H, 11: x.W, 12: cout, 13: cout, 14: 0,
+               15: L.ACT_NONE, 20: 2, 26: rows_per_img, 27: 0, 28: 1},
+            f={1: w_qk.omni_oscale}))
+        self.keep += [w_qk, ws] + ([bias] if bias is not None else [])
+        self.flops += 2 * M * cout * K + 2 * M * cout * 16     # the projection and the 32 x 32 score products per token and group
+        self.bytes += 4 * (M * K + cout * K + (M // 256) * (cout // 64) * 1024)
+
     def pack_weight_patch(self, w: torch.Tensor, ld: int = 4) -> torch.Tensor:
         """[Cout, Cin <= ld, k, k] f32 (k <= 8) -> split-f16 weight of the ROW-PATCH form of the convolution (conv_patch):
         [Cout][k rows][8 pixels][ld channels], zero beyond tap k - 1 and beyond channel Cin - 1."""
