@@ -2815,6 +2815,13 @@ int by_dtype(int dtype, const char* name, F32 f32, F16 f16) {
   return OMNI_OK;
 }
 
+// launch(T{}, std::bool_constant<SCORES>{}) for the op's element type and for whether it has a log-probability output
+template <typename L>
+int by_dtype_scores(int dtype, bool scores, const char* name, L launch) {
+  return scores ? by_dtype(dtype, name, [&] { launch(float{}, std::true_type{}); }, [&] { launch(half_t{}, std::true_type{}); })
+                : by_dtype(dtype, name, [&] { launch(float{}, std::false_type{}); }, [&] { launch(half_t{}, std::false_type{}); });
+}
+
 }  // namespace
 
 int omni_launch_dwconv3(const omni_op_t* op, hipStream_t s) {
@@ -3044,6 +3051,24 @@ static int launch_attn_decode(const omni_op_t* op, hipStream_t s) {
   return OMNI_OK;
 }
 
+// the end of every decode-step launcher: i11 asks for the step counter (p6) to be advanced behind the step's kernel
+static int finish_step(const omni_op_t* op, hipStream_t s) {
+  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
+  OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
+// the arguments that OMNI_OP_GREEDY_STEP and OMNI_OP_GREEDY_CTRL_STEP share
+static GreedyArgs greedy_args_from_op(const omni_op_t* op) {
+  GreedyArgs a{};
+  a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (int*)op->p[2]; a.finished = (int*)op->p[3];
+  a.step = (const int*)op->p[6];
+  a.B = op->i[0]; a.V = op->i[1]; a.ldl = op->i[2]; a.T = op->i[3]; a.max_new = op->i[4]; a.ngram = op->i[5];
+  a.bos = op->i[6]; a.eos = op->i[7]; a.pad = op->i[8]; a.forced_bos = op->i[9]; a.forced_eos = op->i[10];
+  a.logp = (float*)op->p[4];
+  return a;
+}
+
 // the target-score form of OMNI_OP_GREEDY_STEP (p5 set): p3, i4..i10 are not read
 static int launch_score(const omni_op_t* op, hipStream_t s) {
   ScoreArgs a{};
@@ -3057,57 +3082,31 @@ static int launch_score(const omni_op_t* op, hipStream_t s) {
   int rc = by_dtype(op->dtype, "greedy_step",
       [&] { hipLaunchKernelGGL(score_step_kernel<float>, dim3(a.B), dim3(256), 0, s, a); },
       [&] { hipLaunchKernelGGL(score_step_kernel<half_t>, dim3(a.B), dim3(256), 0, s, a); });
-  if (rc) return rc;
-  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
-  OMNI_HIP_CHECK(hipGetLastError());
-  return OMNI_OK;
+  return rc ? rc : finish_step(op, s);
 }
 
 static int launch_greedy(const omni_op_t* op, hipStream_t s) {
   if (op->p[5] || op->p[7]) return launch_score(op, s);
-  GreedyArgs a{};
-  a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (int*)op->p[2]; a.finished = (int*)op->p[3];
-  a.step = (const int*)op->p[6];
-  a.B = op->i[0]; a.V = op->i[1]; a.ldl = op->i[2]; a.T = op->i[3]; a.max_new = op->i[4]; a.ngram = op->i[5];
-  a.bos = op->i[6]; a.eos = op->i[7]; a.pad = op->i[8]; a.forced_bos = op->i[9]; a.forced_eos = op->i[10];
+  GreedyArgs a = greedy_args_from_op(op);
   OMNI_REQUIRE(a.logits && a.ids && a.finished && a.step && a.B > 0 && a.V > 0 && a.T >= a.max_new + 1, "greedy_step: bad arguments");
-  a.logp = (float*)op->p[4];
   if (a.ngram > 0 && a.max_new - a.ngram + 1 > 32) {
     // more n-gram start positions in a full history than the list of greedy_step_kernel holds: the exact (bitmap) form
     const size_t lds = ((size_t)((a.V + 31) >> 5) + (size_t)a.T) * 4;
     OMNI_REQUIRE(lds <= 48 * 1024, "greedy_step: a vocabulary of %d and %d positions exceed the ban LDS", a.V, a.T);
-    int rl = a.logp ? by_dtype(op->dtype, "greedy_step",
-        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<float, true>), dim3(a.B), dim3(256), lds, s, a); },
-        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<half_t, true>), dim3(a.B), dim3(256), lds, s, a); })
-                    : by_dtype(op->dtype, "greedy_step",
-        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<float, false>), dim3(a.B), dim3(256), lds, s, a); },
-        [&] { hipLaunchKernelGGL((greedy_step_long_kernel<half_t, false>), dim3(a.B), dim3(256), lds, s, a); });
-    if (rl) return rl;
-    if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
-    OMNI_HIP_CHECK(hipGetLastError());
-    return OMNI_OK;
+    int rl = by_dtype_scores(op->dtype, a.logp != nullptr, "greedy_step", [&](auto t, auto sc) {
+      hipLaunchKernelGGL((greedy_step_long_kernel<decltype(t), decltype(sc)::value>), dim3(a.B), dim3(256), lds, s, a); });
+    return rl ? rl : finish_step(op, s);
   }
-  int rc = a.logp ? by_dtype(op->dtype, "greedy_step",
-      [&] { hipLaunchKernelGGL((greedy_step_kernel<float, true>), dim3(a.B), dim3(256), 0, s, a); },
-      [&] { hipLaunchKernelGGL((greedy_step_kernel<half_t, true>), dim3(a.B), dim3(256), 0, s, a); })
-                  : by_dtype(op->dtype, "greedy_step",
-      [&] { hipLaunchKernelGGL((greedy_step_kernel<float, false>), dim3(a.B), dim3(256), 0, s, a); },
-      [&] { hipLaunchKernelGGL((greedy_step_kernel<half_t, false>), dim3(a.B), dim3(256), 0, s, a); });
-  if (rc) return rc;
-  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
-  OMNI_HIP_CHECK(hipGetLastError());
-  return OMNI_OK;
+  int rc = by_dtype_scores(op->dtype, a.logp != nullptr, "greedy_step", [&](auto t, auto sc) {
+    hipLaunchKernelGGL((greedy_step_kernel<decltype(t), decltype(sc)::value>), dim3(a.B), dim3(256), 0, s, a); });
+  return rc ? rc : finish_step(op, s);
 }
 
 // OMNI_OP_GREEDY_CTRL_STEP: the generating form of launch_greedy with the control block p7 (i12 bytes); one kernel for every setting
 static int launch_greedy_ctrl(const omni_op_t* op, hipStream_t s) {
   GreedyCtrlArgs c{};
-  GreedyArgs& a = c.g;
-  a.logits = op->p[0]; a.bias = (const float*)op->p[1]; a.ids = (int*)op->p[2]; a.finished = (int*)op->p[3];
-  a.step = (const int*)op->p[6];
-  a.B = op->i[0]; a.V = op->i[1]; a.ldl = op->i[2]; a.T = op->i[3]; a.max_new = op->i[4]; a.ngram = op->i[5];
-  a.bos = op->i[6]; a.eos = op->i[7]; a.pad = op->i[8]; a.forced_bos = op->i[9]; a.forced_eos = op->i[10];
-  a.logp = (float*)op->p[4];
+  c.g = greedy_args_from_op(op);
+  const GreedyArgs& a = c.g;
   c.ctrl = (const unsigned*)op->p[7]; c.ctrl_bytes = op->i[12];
   OMNI_REQUIRE(a.logits && a.ids && a.finished && a.step && a.B > 0 && a.V > 0 && a.ldl >= a.V && a.T >= a.max_new + 1 && a.max_new >= 1,
                "greedy_ctrl_step: bad arguments");
@@ -3118,16 +3117,9 @@ static int launch_greedy_ctrl(const omni_op_t* op, hipStream_t s) {
                "two bitmaps over a vocabulary of %d (%lld bytes)", c.ctrl_bytes, a.V, OMNI_GEN_CTRL_HEADER_BYTES + 8 * nw);
   const size_t lds = ((size_t)2 * nw + (size_t)a.T + OMNI_GEN_CTRL_MAX_BAD) * 4;
   OMNI_REQUIRE(lds <= 48 * 1024, "greedy_ctrl_step: a vocabulary of %d and %d positions exceed the bitmap LDS", a.V, a.T);
-  int rc = a.logp ? by_dtype(op->dtype, "greedy_ctrl_step",
-      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<float, true>), dim3(a.B), dim3(256), lds, s, c); },
-      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<half_t, true>), dim3(a.B), dim3(256), lds, s, c); })
-                  : by_dtype(op->dtype, "greedy_ctrl_step",
-      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<float, false>), dim3(a.B), dim3(256), lds, s, c); },
-      [&] { hipLaunchKernelGGL((greedy_ctrl_step_kernel<half_t, false>), dim3(a.B), dim3(256), lds, s, c); });
-  if (rc) return rc;
-  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
-  OMNI_HIP_CHECK(hipGetLastError());
-  return OMNI_OK;
+  int rc = by_dtype_scores(op->dtype, a.logp != nullptr, "greedy_ctrl_step", [&](auto t, auto sc) {
+    hipLaunchKernelGGL((greedy_ctrl_step_kernel<decltype(t), decltype(sc)::value>), dim3(a.B), dim3(256), lds, s, c); });
+  return rc ? rc : finish_step(op, s);
 }
 
 static int launch_beam(const omni_op_t* op, hipStream_t s) {
@@ -3146,10 +3138,7 @@ static int launch_beam(const omni_op_t* op, hipStream_t s) {
   int rc = by_dtype(op->dtype, "beam_step",
       [&] { hipLaunchKernelGGL(beam_step_kernel<float>, dim3(a.B), dim3(256), lds, s, a); },
       [&] { hipLaunchKernelGGL(beam_step_kernel<half_t>, dim3(a.B), dim3(256), lds, s, a); });
-  if (rc) return rc;
-  if (op->i[11]) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, s, (int*)op->p[6]);
-  OMNI_HIP_CHECK(hipGetLastError());
-  return OMNI_OK;
+  return rc ? rc : finish_step(op, s);
 }
 
 static int launch_crop_resize(const omni_op_t* op, hipStream_t s) {
