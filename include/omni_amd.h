@@ -362,8 +362,44 @@ enum {
    * <= 48 KiB, else OMNI_E_ARG (17 KB at a vocabulary of 51289 and T = 1025).  A neutral block (penalty 1.0, n-gram -1, nothing else
    * set) gives bit for bit what OMNI_OP_GREEDY_STEP gives.  Value 26; plan bundles and the model-level entry points do not use it. */
   OMNI_OP_GREEDY_CTRL_STEP = OMNI_OP__COUNT,   /* 26, the number the end mark of the list above has */
+  /* greedy decoding step over a CLOSED VOCABULARY: OMNI_OP_GREEDY_STEP's generating form (p0..p4, p6 and i0..i11 mean exactly what
+   * they mean there, p4 = token log-probabilities or NULL) with transformers' PrefixConstrainedLogitsProcessor for a fixed set of
+   * labels: the set is a trie in DEVICE memory, read at every step — one captured step graph serves every vocabulary.
+   *  p5 node i32[B], read and written: the row's trie node, 0 = root (the caller zeroes it before the first step), -1 = left the trie
+   *  p7 trie block (layout below, 4-byte aligned)   i12 its size in bytes
+   * Per row, in transformers' order (generation/utils.py _get_logits_processor): NoRepeatNGram (i5; exact for any history),
+   * PrefixConstrained, ForcedBOS, ForcedEOS — x = logits[tok] + final_logits_bias[tok] in f32 is taken ONLY at the edge tokens of
+   * node[b]; nothing else of the row's logits is read.  Edges whose token the n-gram ban of ids[b][0..st] hits are at -inf.  Then the
+   * arg-max (lowest token id among equals), or the forced token at a forced position; pad for finished rows and the EOS bookkeeping
+   * of OMNI_OP_GREEDY_STEP; with p4, log_softmax over the allowed, unbanned children at the token — exactly 0.0 at a forced
+   * position, for a finished row and at a node with one allowed child.  node[b] becomes the child the emitted token leads to (the
+   * forced token moves it too), -1 when no edge of the node carries that token; finished rows leave it alone.  A row at node -1, at a
+   * node without edges, or whose edges are all -inf / NaN emits id 0 (its log-probability is unspecified), as the other greedy
+   * kernels do for a row without a finite entry.
+   * Trie block, 4-byte words, CSR (struct omni_vocab_trie is the header):
+   *  words 0..7 {n_nodes (1..OMNI_VOCAB_MAX_NODES), n_edges, longest label in tokens, 0, 0, 0, 0, 0}
+   *  then first i32[n_nodes + 1] (edges of node k = [first[k], first[k + 1])), edge_tok i32[n_edges] (ascending within a node),
+   *  edge_dst i32[n_edges] (the child node).  Node 0 is the root; in a trie n_edges = n_nodes - 1.
+   * i12 >= 32 + 4 (n_nodes + 1 + 2 n_edges), with n_nodes and n_edges as the header in p7 holds them when omni_op_launch /
+   * omni_plan_create see the op (they read the 32-byte header back), else OMNI_E_ARG; with the pointer check on, p7 + i12 lies inside
+   * one allocation.  The kernel itself never reads beyond i12 bytes whatever the block says later: the header's counts are clamped
+   * to i12, edge ranges to the edge arrays, and edge tokens outside 0..i1-1 are skipped.
+   * One kernel, greedy_vocab_step_kernel (csrc/vocab_step.hip).  LDS: i3 x 4 bytes + the reduction arrays <= 48 KiB, else
+   * OMNI_E_ARG.  Plan bundles and the model-level entry points do not use it. */
+  OMNI_OP_GREEDY_VOCAB_STEP = OMNI_OP_GREEDY_CTRL_STEP + 1,   /* 27 (spelled like the kind above: the literally numbered kinds stay 1..24) */
   OMNI_OP__END
 };
+
+/* header of the trie block of OMNI_OP_GREEDY_VOCAB_STEP (p7); first / edge_tok / edge_dst follow it, see the op */
+#define OMNI_VOCAB_HEADER_BYTES 32
+#define OMNI_VOCAB_MAX_NODES 65536     /* nodes of a vocabulary's trie, the root included */
+#define OMNI_VOCAB_MAX_LABEL 64        /* tokens of a label */
+typedef struct omni_vocab_trie {
+  int32_t n_nodes;         /* nodes, the root (node 0) included */
+  int32_t n_edges;         /* edges = n_nodes - 1 */
+  int32_t longest;         /* tokens of the longest label */
+  int32_t reserved[5];
+} omni_vocab_trie_t;
 
 /* header of the control block of OMNI_OP_GREEDY_CTRL_STEP (p7); the variable parts follow it, see the op */
 #define OMNI_GEN_CTRL_HEADER_BYTES 32

@@ -21,6 +21,7 @@ OP_DWCONV3, OP_LAYERNORM, OP_ATTN_ROWS, OP_CHAN_ATTN, OP_PROJ_PREP, OP_ASSEMBLE 
 OP_EMBED_STEP, OP_ATTN_DECODE, OP_GREEDY_STEP, OP_CROP_RESIZE, OP_DWCONV3_LN, OP_SPLIT_CONVERT, OP_GLUE = 14, 15, 16, 17, 18, 19, 20
 OP_OVERLAY, OP_PNG_PACK, OP_PNG_DEFLATE, OP_MLP_FUSED, OP_BEAM_STEP = 21, 22, 23, 24, 25
 OP_GREEDY_CTRL_STEP = 26
+OP_GREEDY_VOCAB_STEP = 27
 CAND_BYTES = 32
 ABI_VERSION = 3         # include/omni_amd.h::OMNI_ABI_VERSION — a library built from other headers is refused at load time
 

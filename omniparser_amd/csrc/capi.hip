@@ -73,6 +73,7 @@ static int dispatch(const omni_op_t* op, hipStream_t s) {
     case OMNI_OP_ATTN_ROWS: case OMNI_OP_CHAN_ATTN: case OMNI_OP_ATTN_DECODE: return omni_launch_attention(op, s);
     case OMNI_OP_PROJ_PREP: case OMNI_OP_ASSEMBLE: case OMNI_OP_EMBED_STEP: case OMNI_OP_GREEDY_STEP:
     case OMNI_OP_BEAM_STEP: case OMNI_OP_GREEDY_CTRL_STEP: case OMNI_OP_CROP_RESIZE: return omni_launch_misc(op, s);
+    case OMNI_OP_GREEDY_VOCAB_STEP: return omni_launch_vocab_step(op, s);
     default:
       omni_set_error("unknown op kind %d", op->kind);
       return OMNI_E_ARG;
@@ -154,6 +155,16 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       ext[1] = (long long)i[1] * 4;
       ext[2] = ext[4] = rows * T * 4;
       ext[3] = rows * 4;
+      ext[6] = 4;
+      ext[7] = i[12];
+      break;
+    }
+    case OMNI_OP_GREEDY_VOCAB_STEP: {                        // whole buffers; p5: the rows' nodes; p7: the i12 bytes of the trie block
+      const long long rows = i[0], T = i[3];
+      ext[0] = rows > 0 ? ((rows - 1) * i[2] + i[1]) * esz : 1;
+      ext[1] = (long long)i[1] * 4;
+      ext[2] = ext[4] = rows * T * 4;
+      ext[3] = ext[5] = rows * 4;
       ext[6] = 4;
       ext[7] = i[12];
       break;
@@ -298,10 +309,43 @@ static int check_ctrl_block(const omni_op_t* op, int index) {
   return OMNI_OK;
 }
 
+// OMNI_OP_GREEDY_VOCAB_STEP: i12 must cover what the header of the trie block (p7, device memory) claims — the header, first[n_nodes + 1]
+// and two edge arrays of n_edges words.  Read back like the control block's header above, at the same two places; the kernel clamps on
+// its own whatever the block holds later.
+static int check_trie_block(const omni_op_t* op, int index) {
+  if (op->kind != OMNI_OP_GREEDY_VOCAB_STEP) return OMNI_OK;
+  const long long bytes = op->i[12];
+  if (!op->p[7] || bytes < OMNI_VOCAB_HEADER_BYTES + 4) {
+    omni_set_error("op %d (greedy_vocab_step): a trie block of %lld bytes (i12) at p7 = %p cannot hold the header and one node (%d bytes)",
+                   index, bytes, op->p[7], OMNI_VOCAB_HEADER_BYTES + 4);
+    return OMNI_E_ARG;
+  }
+  omni_vocab_trie_t h;
+  hipError_t e = hipMemcpy(&h, op->p[7], sizeof h, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    omni_set_error("op %d (greedy_vocab_step): the header of the trie block p7 = %p cannot be read (%s)", index, op->p[7], hipGetErrorString(e));
+    return OMNI_E_ARG;
+  }
+  if (h.n_nodes < 1 || h.n_nodes > OMNI_VOCAB_MAX_NODES || h.n_edges < 0 || h.n_edges >= h.n_nodes) {
+    omni_set_error("op %d (greedy_vocab_step): the trie block claims %d nodes and %d edges (1..%d nodes, fewer edges than nodes)", index,
+                   h.n_nodes, h.n_edges, OMNI_VOCAB_MAX_NODES);
+    return OMNI_E_ARG;
+  }
+  const long long need = OMNI_VOCAB_HEADER_BYTES + 4LL * (h.n_nodes + 1 + 2LL * h.n_edges);
+  if (bytes < need) {
+    omni_set_error("op %d (greedy_vocab_step): the trie block's header claims %d nodes and %d edges = %lld bytes, i12 says %lld",
+                   index, h.n_nodes, h.n_edges, need, bytes);
+    return OMNI_E_ARG;
+  }
+  return OMNI_OK;
+}
+
 extern "C" int omni_op_launch(const omni_op_t* op, void* stream) {
   if (!op) { omni_set_error("omni_op_launch: null op"); return OMNI_E_ARG; }
   if (check_ptrs_enabled()) { int rc = check_op_ptrs(op, 0); if (rc) return rc; }
   if (int rc = check_ctrl_block(op, 0)) return rc;
+  if (int rc = check_trie_block(op, 0)) return rc;
   return dispatch(op, (hipStream_t)stream);
 }
 
@@ -322,6 +366,7 @@ extern "C" int omni_plan_create(const omni_op_t* ops, int n_ops, omni_plan_t** o
   if (check_ptrs_enabled())
     for (int i = 0; i < n_ops; ++i) { int rc = check_op_ptrs(&ops[i], i); if (rc) return rc; }
   for (int i = 0; i < n_ops; ++i) { int rc = check_ctrl_block(&ops[i], i); if (rc) return rc; }
+  for (int i = 0; i < n_ops; ++i) { int rc = check_trie_block(&ops[i], i); if (rc) return rc; }
   omni_plan* p = new omni_plan();
   p->ops.assign(ops, ops + n_ops);
   *out = p;

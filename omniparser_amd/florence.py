@@ -410,7 +410,168 @@ class GenerationControls:
         return words
 
 
-FORCE_ROWS = (1, 4, 8)             # candidate rows per crop of a teacher-forced plan (`Florence2Captioner.score`)
+# ---- closed vocabularies (OMNI_OP_GREEDY_VOCAB_STEP): the ONE Python mirror of the trie block of include/omni_amd.h
+VOCAB_HEADER_WORDS = 8             # struct omni_vocab_trie: i32 n_nodes | n_edges | longest | 0 | 0 | 0 | 0 | 0
+VOCAB_TRIE_FIELDS = ("n_nodes", "n_edges", "longest", "reserved")
+VOCAB_MAX_NODES = 65536            # OMNI_VOCAB_MAX_NODES: nodes of a vocabulary's trie, the root included
+VOCAB_MAX_LABEL = 64               # OMNI_VOCAB_MAX_LABEL: tokens of a label
+
+
+def vocab_trie_words(n_nodes: int = VOCAB_MAX_NODES) -> int:
+    """4-byte words of the trie block of a trie of n_nodes nodes (n_nodes - 1 edges): header, first[n_nodes + 1], edge_tok, edge_dst
+    (the default: the largest block there is, the capacity of a vocabulary plan's buffer)"""
+    return VOCAB_HEADER_WORDS + int(n_nodes) + 1 + 2 * (int(n_nodes) - 1)
+
+
+def ngram_banned(prefix, n):
+    """the tokens transformers' NoRepeatNGramLogitsProcessor(n) bans behind `prefix` (a list of ids)"""
+    banned, m = set(), len(prefix)
+    if n > 0 and m + 1 >= n:
+        tail = prefix[m - (n - 1):]
+        for i in range(m - n + 1):
+            if prefix[i:i + n - 1] == tail:
+                banned.add(prefix[i + n - 1])
+    return banned
+
+
+class CaptionVocabulary:
+    """A closed vocabulary of captions as one value object: a set of labels, each a list of token ids in the format
+    `Florence2Captioner.score` takes and `FlorenceProcessor.prompt_ids` returns (the generated positions 1..L: the checkpoint's forced
+    BOS when it has one, the text, EOS).  Greedy decoding with it (`generate(vocabulary=...)`, OMNI_OP_GREEDY_VOCAB_STEP) returns
+    exactly one of the labels per image: transformers' prefix_allowed_tokens_fn for this set, compiled to a trie that the device
+    reads at every step.  The constructor deduplicates the labels (`labels`: the distinct ones in their first order, what
+    `label_index` counts) and builds the trie; a label that is a prefix of another is fine.  `check` holds the set against a model;
+    `pack` writes the trie block."""
+    __slots__ = ("labels", "longest", "_children", "_end")
+
+    def __init__(self, labels):
+        isint = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        if isinstance(labels, torch.Tensor):
+            labels = labels.tolist()
+        if isinstance(labels, (str, bytes)) or not hasattr(labels, "__iter__"):
+            raise ValueError(f"a vocabulary is a list of labels, each a list of token ids; got {labels!r}")
+        rows = []
+        for lab in labels:
+            if isinstance(lab, torch.Tensor):
+                lab = lab.tolist()
+            if isinstance(lab, (str, bytes)) or not hasattr(lab, "__iter__"):
+                raise ValueError(f"vocabulary: a label must be a list of token ids, got {lab!r}")
+            lab = tuple(lab)
+            if not lab:
+                raise ValueError("vocabulary: an empty label")
+            if len(lab) > VOCAB_MAX_LABEL:
+                raise ValueError(f"vocabulary: a label of {len(lab)} tokens (at most {VOCAB_MAX_LABEL})")
+            bad = [t for t in lab if not isint(t) or t < 0]
+            if bad:
+                raise ValueError(f"vocabulary: token ids must be integers of at least 0, got {bad[0]!r}")
+            rows.append(lab)
+        if not rows:
+            raise ValueError("vocabulary: no label; at least one is needed")
+        self.labels = tuple(dict.fromkeys(rows))
+        self.longest = max(len(lab) for lab in self.labels)
+        self._children, self._end = [{}], {}
+        for k, lab in enumerate(self.labels):
+            node = 0
+            for t in lab:
+                nxt = self._children[node].get(t)
+                if nxt is None:
+                    nxt = len(self._children)
+                    self._children[node][t] = nxt
+                    self._children.append({})
+                node = nxt
+            self._end[node] = k
+        if len(self._children) > VOCAB_MAX_NODES:
+            raise ValueError(f"vocabulary: its trie has {len(self._children)} nodes (at most {VOCAB_MAX_NODES})")
+
+    @classmethod
+    def of(cls, x) -> Optional["CaptionVocabulary"]:
+        """None -> None (no vocabulary); a CaptionVocabulary -> itself; a list of id lists -> its vocabulary"""
+        if x is None or isinstance(x, cls):
+            return x
+        return cls(x)
+
+    @property
+    def n_nodes(self) -> int:
+        return len(self._children)
+
+    def children(self, node: int):
+        """the allowed next tokens at a node, ascending ([] at a leaf or outside the trie)"""
+        return sorted(self._children[node]) if 0 <= node < len(self._children) else []
+
+    def walk(self, tokens, node: int = 0) -> int:
+        """the node reached from `node` along `tokens`, -1 once the path leaves the trie"""
+        for t in tokens:
+            node = self._children[node].get(int(t), -1) if 0 <= node < len(self._children) else -1
+            if node < 0:
+                return -1
+        return node
+
+    def label_of(self, node: int) -> int:
+        """index (into `labels`) of the label that ends at `node`, or -1"""
+        return self._end.get(int(node), -1)
+
+    def label_index(self, generated, eos) -> int:
+        """index of the label a generated row spells (the ids behind the decoder start token, up to and including the first EOS),
+        or -1 when it is none of them"""
+        row = [int(t) for t in generated]
+        if int(eos) not in row:
+            return -1
+        return self.label_of(self.walk(row[:row.index(int(eos)) + 1]))
+
+    def check(self, vocab, max_new_tokens, eos, forced_bos=-1, forced_eos=-1, ngram=0, start=2):
+        """the checks that need the model: ids inside the vocabulary, every label = [forced BOS] text EOS with EOS nowhere else,
+        max_new_tokens holds the longest label (else the output would not be a label), a forced EOS token that is not the EOS token
+        cannot replace a label's last token (it could only at max_new_tokens == the longest label), and no
+        DEAD END: a node where the n-gram ban (size `ngram`) of its own prefix — unique in a trie; the decoder start token `start`
+        included — removes every child, so that no label could be completed there.  ValueError; returns self."""
+        eos, fb, fe = int(eos), -1 if forced_bos is None else int(forced_bos), -1 if forced_eos is None else int(forced_eos)
+        for lab in self.labels:
+            bad = [t for t in lab if t >= vocab]
+            if bad:
+                raise ValueError(f"vocabulary: token id {bad[0]} is outside the vocabulary (0..{vocab - 1})")
+            if lab[-1] != eos:
+                raise ValueError(f"vocabulary: label {list(lab)} does not end in the EOS token ({eos})")
+            if eos in lab[:-1]:
+                raise ValueError(f"vocabulary: label {list(lab)} holds the EOS token ({eos}) before its end")
+            if fb >= 0 and lab[0] != fb:
+                raise ValueError(f"vocabulary: label {list(lab)} does not start with the forced BOS token ({fb}) of this checkpoint")
+        if int(max_new_tokens) < self.longest:
+            raise ValueError(f"vocabulary: max_new_tokens ({max_new_tokens}) is below the longest label ({self.longest} tokens): the "
+                             "output would not be a label")
+        # the forced position max_new_tokens is reached by an unfinished row only when it is the last token of a longest label
+        if fe >= 0 and fe != eos and int(max_new_tokens) == self.longest:
+            raise ValueError(f"vocabulary: the checkpoint forces token {fe} at position max_new_tokens ({max_new_tokens}), which is not "
+                             f"its EOS token ({eos}) and would replace the last token of the longest label: give max_new_tokens of at "
+                             f"least {self.longest + 1}")
+        stack = [(0, [int(start)])]
+        while stack:
+            node, prefix = stack.pop()
+            kids = self._children[node]
+            if not kids:
+                continue
+            forced = (fb >= 0 and len(prefix) == 1) or (fe >= 0 and len(prefix) == int(max_new_tokens))
+            if not forced and not set(kids) - ngram_banned(prefix, int(ngram)):
+                raise ValueError(f"vocabulary: a dead end behind the prefix {prefix} (decoder start token included): the checkpoint's "
+                                 f"no_repeat_ngram_size = {ngram} bans every continuation {sorted(kids)}")
+            for t, nxt in kids.items():
+                stack.append((nxt, prefix + [t]))
+        return self
+
+    def pack(self) -> torch.Tensor:
+        """the trie block as i32 words on the host (include/omni_amd.h OMNI_OP_GREEDY_VOCAB_STEP): header {n_nodes, n_edges, longest
+        label, 0 x 5}, first[n_nodes + 1], edge_tok (ascending within a node), edge_dst"""
+        first, tok, dst = [0], [], []
+        for kids in self._children:
+            for t in sorted(kids):
+                tok.append(t)
+                dst.append(kids[t])
+            first.append(len(tok))
+        n = len(self._children)
+        assert len(tok) == n - 1 and VOCAB_HEADER_WORDS + len(first) + 2 * len(tok) == vocab_trie_words(n)
+        return torch.tensor([n, len(tok), self.longest, 0, 0, 0, 0, 0] + first + tok + dst, dtype=torch.int32)
+
+
+FORCE_ROWS = (1, 4, 8)            # candidate rows per crop of a teacher-forced plan (`Florence2Captioner.score`)
 LABEL_CAPACITIES = (8, 16, 32)     # label tokens per candidate (T - 1 of such a plan)
 
 
@@ -537,12 +698,18 @@ class _StepPlans:
     logp = None
     force = None
     ctrl = None
+    node = None
+    trie = None
 
-    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None, scores=False, force=None, controls=False):
+    def _build_step(self, cap, B, max_new, S, cross_kv, ws=None, beam=None, nkeys=None, scores=False, force=None, controls=False,
+                    vocab=False):
         """nkeys: i32 [crops] valid encoder keys per crop (a prompt shorter than the plan's text capacity: OMNI_OP_ATTN_DECODE p7 of
         the cross-attention), or None = all S
         controls (greedy only): the plan owns `ctrl`, an i32 buffer of the largest control block (`gen_ctrl_words`), and ends in
-        OMNI_OP_GREEDY_CTRL_STEP instead of OMNI_OP_GREEDY_STEP; `set_controls` uploads a call's block before its first step"""
+        OMNI_OP_GREEDY_CTRL_STEP instead of OMNI_OP_GREEDY_STEP; `set_controls` uploads a call's block before its first step
+        vocab (greedy only, with or without scores): the plan owns `node` i32 [B] (every row's trie node, zeroed by `reset`) and `trie`,
+        an i32 buffer of the largest trie block (`vocab_trie_words`), and ends in OMNI_OP_GREEDY_VOCAB_STEP; `set_vocabulary` uploads a
+        call's block before its first step"""
         w, dev, dt = cap.w, cap.device, cap.dtype
         sd = w.sd
         D, nh, lm = w.d_model, w.n_heads, "model.language_model."
@@ -550,6 +717,7 @@ class _StepPlans:
         self.beam = beam
         assert not (force and (beam or scores)), "a teacher-forced plan neither searches nor generates"
         assert not (controls and (beam or force)), "generation controls are a greedy-decoding feature"
+        assert not (vocab and (beam or force or controls)), "a closed vocabulary is a greedy-decoding feature without generation controls"
         self.force = force
         kb = beam[0] if beam else (force or 1)
         crops, B = B, B * kb                               # B = decoder rows from here on
@@ -585,6 +753,15 @@ class _StepPlans:
             self.ctrl.zero_()
             neutral = GenerationControls().pack(w.vocab, w.forced_bos)
             self.ctrl[:neutral.numel()].copy_(neutral)
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()       # omni_plan_create reads the block's header back
+        if vocab:
+            self.node = pd_.raw((B,), torch.int32)
+            self.node.zero_()
+            self.trie = pd_.raw((vocab_trie_words(),), torch.int32)
+            self.trie.zero_()
+            one = CaptionVocabulary([([w.forced_bos] if w.forced_bos >= 0 else []) + [w.eos]]).pack()
+            self.trie[:one.numel()].copy_(one)
             if dev.type == "cuda":
                 torch.cuda.current_stream(dev).synchronize()       # omni_plan_create reads the block's header back
         esz = 4 if dt == L.F32 else 2
@@ -660,6 +837,13 @@ class _StepPlans:
                                     self.ctrl.data_ptr()],
                                  i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: w.bos, 7: w.eos, 8: w.pad,
                                     9: w.forced_bos, 10: w.forced_eos, 11: 1, 12: self.ctrl.numel() * 4}))
+        elif vocab:                                        # the same slots + the rows' trie nodes and the trie block
+            pd_.add_op(L.make_op(L.OP_GREEDY_VOCAB_STEP, dt,
+                                 p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
+                                    self.finished.data_ptr(), self.logp.data_ptr() if scores else None, self.node.data_ptr(),
+                                    self.step.data_ptr(), self.trie.data_ptr()],
+                                 i={0: B, 1: w.vocab, 2: w.vocab, 3: T, 4: max_new, 5: w.ngram, 6: w.bos, 7: w.eos, 8: w.pad,
+                                    9: w.forced_bos, 10: w.forced_eos, 11: 1, 12: self.trie.numel() * 4}))
         else:
             pd_.add_op(L.make_op(L.OP_GREEDY_STEP, dt,
                                  p=[logits.ptr, flb.data_ptr() if flb is not None else None, self.ids.data_ptr(),
@@ -688,6 +872,8 @@ class _StepPlans:
         self.finished.zero_()
         if self.logp is not None:
             self.logp.zero_()
+        if self.node is not None:                          # every row at the root
+            self.node.zero_()
         self.step.zero_()
 
     def _reset_beams(self):
@@ -717,6 +903,12 @@ class _StepPlans:
         behind the block keep what they held; no header makes the kernel read them."""
         assert self.ctrl is not None and block.dtype == torch.int32 and block.numel() <= self.ctrl.numel()
         self.ctrl[:block.numel()].copy_(block, non_blocking=True)
+
+    def set_vocabulary(self, block: torch.Tensor):
+        """a vocabulary plan's trie block on the current stream: `CaptionVocabulary.pack` words from the host.  Words of the buffer
+        behind the block keep what they held; no header makes the kernel read them."""
+        assert self.trie is not None and block.dtype == torch.int32 and block.numel() <= self.trie.numel()
+        self.trie[:block.numel()].copy_(block, non_blocking=True)
 
     def result_ids(self, n: int) -> torch.Tensor:
         """device ids of the first n crops: the greedy rows, or the best finished hypothesis of each crop"""
@@ -756,7 +948,7 @@ class _DecodePlans(_StepPlans):
     n_txt: text capacity of the micro-batches' plans when the prompt is an input (`_CaptionPlans`); `nkeys` is then the merged
     table of valid encoder keys per crop, copied from the micro-batches like the K / V (`_encode_into`)."""
 
-    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, beam=None, n_txt=None, scores=False):
+    def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, beam=None, n_txt=None, scores=False, vocab=False):
         w, dev, dt = cap.w, cap.device, cap.dtype
         self.B, self.R = B, R
         S = (R // 32) ** 2 + 1 + (len(PROMPT_IDS) if n_txt is None else n_txt)
@@ -771,7 +963,7 @@ class _DecodePlans(_StepPlans):
         # recycled allocator memory there can hold NaN bit patterns, whose logits are all-NaN rows (found by the one-process GPU suite)
         self.cross_kv = [pk.alloc(B, S, 1, 2 * w.d_model, zero=True) for _ in range(w.dec_layers)]
         self._keep = pk.keep
-        self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam, nkeys=self.nkeys, scores=scores)
+        self._build_step(cap, B, max_new, S, self.cross_kv, beam=beam, nkeys=self.nkeys, scores=scores, vocab=vocab)
         self.free_evt = None       # recorded behind the decode that last used this plan on another stream (pipelined batches)
         self._warm_up_and_capture(cap, self.step_plan)
 
@@ -792,7 +984,7 @@ class _CaptionPlans(_StepPlans):
     pad token's embedding, attend to the valid keys, stay finite) and are read by nobody."""
 
     def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None,
-                 beam=None, n_txt=None, scores=False, force=None, controls=False):
+                 beam=None, n_txt=None, scores=False, force=None, controls=False, vocab=False):
         w, dev, dt = cap.w, cap.device, cap.dtype
         if arena is not None:
             n_txt = arena.n_txt
@@ -1102,7 +1294,8 @@ class _CaptionPlans(_StepPlans):
                 self.encode_plan.capture(stream or cap.stream)
             return
         # ---------------- decoder step plan (for a single micro-batch; batches of several micro-batches decode through _DecodePlans)
-        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys, scores=scores, force=force, controls=controls)
+        self._build_step(cap, B, max_new, S, self.cross_kv, pb.ws, beam=beam, nkeys=self.nkeys, scores=scores, force=force, controls=controls,
+                         vocab=vocab)
         self._warm_up_and_capture(cap, self.encode_plan, self.step_plan)
 
     def set_prompt(self, ids: torch.Tensor, nkeys: torch.Tensor, n: int):
@@ -1329,27 +1522,39 @@ class Florence2Captioner:
         return (k, lp, es)
 
     @torch.inference_mode()
-    def decode_plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False) -> _DecodePlans:
+    def decode_plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False, vocab=False) -> _DecodePlans:
         """slot: the pipelined stream (pipeline.py::parse_stream) decodes batch i on its own HIP stream while batch i+1 encodes, so it
         alternates between two decode plans (8 GB of cross-attention K/V each at 384 rows, 768x768 crops).  beam: see
-        `beam_config` (B crops = B k decoder rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`)."""
+        `beam_config` (B crops = B k decoder rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`).  vocab (greedy
+        only): the plan that ends in OMNI_OP_GREEDY_VOCAB_STEP (`plans`); part of the cache key."""
         self.check_max_new(max_new, beam)
+        if vocab and beam:
+            raise ValueError("a closed vocabulary is applied by greedy decoding only (no beam search)")
         key = ("dec", B, R, max_new) if slot == 0 else ("dec", B, R, max_new, slot)
         if beam or n_txt is not None:
             key = ("dec", B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),))
         if scores:                     # token log-probabilities (greedy): a plan set of its own, like a beam configuration
             key = ("dec", B, R, max_new, slot, beam) + (() if n_txt is None else (("txt", n_txt),)) + ("scores",)
+        if vocab:
+            key = ("dec", B, R, max_new, slot, None) + (() if n_txt is None else (("txt", n_txt),)) + (("scores",) if scores else ()) + ("vocab",)
+            return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, n_txt=n_txt, scores=scores, vocab=True))
         return self._cached_plan(key, lambda: _DecodePlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
     @torch.inference_mode()
-    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False, force=None, controls=False) -> _CaptionPlans:
+    def plans(self, B, R, max_new, slot=0, beam=None, n_txt=None, scores=False, force=None, controls=False, vocab=False) -> _CaptionPlans:
         """slot 1 = a second, independent set of buffers of the same capacity: the pipelined stream (pipeline.py::parse_stream) keeps two
         128-crop micro-batches in flight on two HIP streams (~25 GB of activations each at 768x768 with activation reuse, 60 GB without).
         beam: see `beam_config` (the step plan decodes B k rows).  n_txt: text capacity of a batch with a prompt (`prompt_batch`);
         it is part of the cache key, None = the default prompt's plan.  controls (greedy only): the plan that ends in
         OMNI_OP_GREEDY_CTRL_STEP and owns a control block (`_StepPlans.set_controls`); part of the cache key beside `scores`, and
-        only ever built by a call with non-neutral `GenerationControls` — one plan serves every setting."""
+        only ever built by a call with non-neutral `GenerationControls` — one plan serves every setting.  vocab (greedy only, no
+        controls): the plan that ends in OMNI_OP_GREEDY_VOCAB_STEP and owns the rows' trie nodes and a trie buffer
+        (`_StepPlans.set_vocabulary`); part of the cache key beside `scores` and `controls`, only ever built by a call with a
+        `CaptionVocabulary` — one plan and graph serve every vocabulary."""
         self.check_max_new(max_new, beam)
+        if vocab and (beam or force or controls):
+            raise ValueError("a closed vocabulary is applied by greedy decoding only (no beam search, no teacher-forced scoring, no "
+                             "generation controls)")
         if controls and (beam or force):
             raise ValueError("generation controls are applied by greedy decoding only (no beam search, no teacher-forced scoring)")
         key = (B, R, max_new) if slot == 0 else (B, R, max_new, slot)
@@ -1363,6 +1568,9 @@ class Florence2Captioner:
         if controls:
             key = (B, R, max_new, slot, None) + (() if n_txt is None else (("txt", n_txt),)) + (("scores",) if scores else ()) + ("controls",)
             return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, n_txt=n_txt, scores=scores, controls=True))
+        if vocab:
+            key = (B, R, max_new, slot, None) + (() if n_txt is None else (("txt", n_txt),)) + (("scores",) if scores else ()) + ("vocab",)
+            return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, n_txt=n_txt, scores=scores, vocab=True))
         return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
     def generation_controls(self, controls, max_new_tokens, beam=None) -> Optional[GenerationControls]:
@@ -1377,6 +1585,21 @@ class Florence2Captioner:
             raise ValueError("generation controls (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, "
                              "begin_suppress_tokens, bad_words_ids) are not supported with beam search (num_beams > 1): greedy decoding only")
         return gc
+
+    def caption_vocabulary(self, vocabulary, max_new_tokens, beam=None, controls=None) -> Optional[CaptionVocabulary]:
+        """`vocabulary` (None, a list of labels as id lists, or a CaptionVocabulary) checked against this model, before anything
+        touches a device: None when there is none, else the checked object.  ValueError: a bad label (`CaptionVocabulary`,
+        `CaptionVocabulary.check`), or a vocabulary together with beam search or with non-neutral generation controls (`controls`:
+        what `generation_controls` returned) — neither path reads the trie."""
+        if vocabulary is None:
+            return None
+        if beam:
+            raise ValueError("a closed vocabulary (vocabulary=...) is not supported with beam search (num_beams > 1): greedy decoding only")
+        if controls is not None:
+            raise ValueError("a closed vocabulary (vocabulary=...) is not supported together with generation controls (repetition_penalty, "
+                             "no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, bad_words_ids)")
+        w = self.w
+        return CaptionVocabulary.of(vocabulary).check(w.vocab, max_new_tokens, w.eos, w.forced_bos, w.forced_eos, w.ngram, w.start)
 
     # ---- prompts
     def prompt_batch(self, rows, R):
@@ -1530,7 +1753,7 @@ class Florence2Captioner:
     def generate(self, input_ids=None, pixel_values=None, max_new_tokens=20, num_beams=1, do_sample=False, num_return_sequences=1,
                  length_penalty=None, early_stopping=None, return_dict_in_generate=False, attention_mask=None,
                  repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None,
-                 begin_suppress_tokens=None, bad_words_ids=None, **kw):
+                 begin_suppress_tokens=None, bad_words_ids=None, vocabulary=None, **kw):
         """hf-compatible entry point (ref:util/utils.py:125).  pixel_values: [B,3,R,R] float (NCHW).
 
         input_ids [B, n_img + L]: the first n_img = (R / 32)^2 + 1 columns must be the image placeholder token (anything else is a
@@ -1564,8 +1787,23 @@ class Florence2Captioner:
         without controls (or with neutral ones: penalty 1.0, min_new_tokens 0, empty lists) runs the plans it always ran.
         ValueError before anything reaches the device: a value outside its range, a token id outside the vocabulary, the EOS /
         forced BOS / forced EOS token in suppress_tokens, begin_suppress_tokens or as a single-token bad word, and any non-neutral
-        control together with num_beams > 1.  Not supported: min_length, sequence_bias, the encoder-side processors,
-        prefix_allowed_tokens_fn, sampling.
+        control together with num_beams > 1.  Not supported: min_length, sequence_bias, the encoder-side processors, sampling.
+
+        vocabulary (greedy decoding): a closed set of captions — a list of labels, each a list of token ids as
+        `FlorenceProcessor.prompt_ids` returns them ([forced BOS] text EOS), or a `CaptionVocabulary`.  Every returned row is then
+        the decoder start token + exactly one label + padding: what transformers' generate(prefix_allowed_tokens_fn=fn) returns
+        when fn walks the trie of the labels, computed on the device by OMNI_OP_GREEDY_VOCAB_STEP, which reads the trie from device
+        memory (one plan and graph for every vocabulary; thousands of labels cost one decode).  With output_scores the
+        `token_logprobs` are log-softmax values over the allowed continuations (0 where only one is left), so their sum is the
+        label's log-probability among the labels.  return_dict_in_generate=True adds `.label_index` i64 [B]: the label's index
+        in the deduplicated vocabulary (`CaptionVocabulary.labels`), -1 for a row that ended outside it (degenerate logits only).
+        Works with a caller's prompt and any max_new_tokens from the longest label up.  ValueError before anything reaches the
+        device: a label that is empty, longer than 64 tokens, not ending in EOS, holding EOS elsewhere, not starting with the
+        forced BOS, with an id outside the vocabulary, a trie of more than 65536 nodes, max_new_tokens below the longest label, a
+        prefix whose continuations the checkpoint's no_repeat_ngram_size all bans, and a vocabulary together with num_beams > 1 or
+        with any non-neutral generation control (an explicit no_repeat_ngram_size included).  vocabulary=None is the call as it was.
+        The `prefix_allowed_tokens_fn` keyword itself is part of **kw and IGNORED: a Python callable cannot run inside a captured
+        step graph on the device — pass the set of labels as `vocabulary` instead.
 
         Any OTHER keyword argument (**kw) is accepted and IGNORED, as it always was: transformers callers pass use_cache,
         output_attentions and the like, which change nothing here.
@@ -1584,6 +1822,7 @@ class Florence2Captioner:
         controls = self.generation_controls(dict(zip(GEN_CTRL_KEYS, (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
                                                                      suppress_tokens, begin_suppress_tokens, bad_words_ids))),
                                             max_new_tokens, beam)
+        vocab = self.caption_vocabulary(vocabulary, max_new_tokens, beam, controls)
         k = beam[0] if beam else 1
         if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= k:
             raise ValueError(f"num_return_sequences must be in 1..num_beams ({k}), got {num_return_sequences!r}")
@@ -1594,21 +1833,29 @@ class Florence2Captioner:
 
             def fill(cp, s, n):
                 cp.x_in.t[:n, :, :, :3] = pixel_values[s:s + n].to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
-            parts = self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill, prompt, output_scores, controls)
+            parts = self._caption_chunks(pixel_values, Bn, 128, R, max_new_tokens, beam, fill, prompt, output_scores, controls, vocab)
+            extra = {"label_index": self.label_indices(vocab, parts, output_scores)} if vocab else {}
             if output_scores:
                 seq, logp = self._results_scores(parts)
-                return SimpleNamespace(sequences=seq, sequences_scores=None, token_logprobs=logp)
+                return SimpleNamespace(sequences=seq, sequences_scores=None, token_logprobs=logp, **extra)
             seq, scores = self._results(parts, beam, num_return_sequences)
-        return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
+        return SimpleNamespace(sequences=seq, sequences_scores=scores, **extra) if return_dict_in_generate else seq
 
-    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False, controls=None):
+    def label_indices(self, vocab: CaptionVocabulary, parts, scores=False) -> torch.Tensor:
+        """i64 [n]: per row of the per-chunk greedy `_run` results the index of the label it spells in `vocab.labels`, -1 for none"""
+        rows = [r for p in parts for r in (p[0] if scores else p)[:, 1:].tolist()]
+        return torch.tensor([vocab.label_index(r, self.w.eos) for r in rows], dtype=torch.long)
+
+    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False, controls=None, vocab=None):
         """encode + decode n_all images in chunks of `chunk` on the captioner's stream, each on the plan of its bucket: fill(cp, s, n)
         writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  prompt: `prompt_batch`
         of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results` (scores: plans that
         also return the token log-probabilities, for `_results_scores`).  controls: non-neutral `GenerationControls` (None = the
-        plans without them): every chunk runs on a controls plan, its block uploaded on the stream before the first step."""
+        plans without them): every chunk runs on a controls plan, its block uploaded on the stream before the first step.  vocab: a
+        checked `CaptionVocabulary` (None = none): every chunk runs on a vocabulary plan, the trie block uploaded the same way."""
         n_txt = prompt[2] if prompt else None
         block = controls.pack(self.w.vocab, self.w.forced_bos) if controls else None
+        trie = vocab.pack() if vocab else None
         chunk = min(chunk, self.long_plan_rows(max_new_tokens, beam[0] if beam else 1))     # 128 up to T = 227: as before
         if src.is_cuda:                                     # pixels / a screenshot the caller is still producing on its own stream
             self.stream.wait_stream(torch.cuda.current_stream(src.device))
@@ -1616,11 +1863,13 @@ class Florence2Captioner:
         for s in range(0, n_all, chunk):
             n = min(chunk, n_all - s)
             cp = self.plans(self.bucket(n), R, max_new_tokens, beam=beam, n_txt=n_txt, **({"scores": True} if scores else {}),
-                            **({"controls": True} if controls else {}))
+                            **({"controls": True} if controls else {}), **({"vocab": True} if vocab else {}))
             with torch.cuda.stream(self.stream):
                 cp.reset()
                 if controls:
                     cp.set_controls(block)
+                if vocab:
+                    cp.set_vocabulary(trie)
                 fill(cp, s, n)
                 if prompt:
                     cp.set_prompt(prompt[0][s:s + n].to(self.device, non_blocking=True), prompt[1][s:s + n].to(self.device, non_blocking=True), n)
@@ -1656,7 +1905,7 @@ class Florence2Captioner:
 
     @torch.inference_mode()
     def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None,
-                      prompt_ids=None, return_scores=None, controls=None):
+                      prompt_ids=None, return_scores=None, controls=None, vocabulary=None):
         """Fused fast path: crops are cut, resized (cv2-bilinear 64x64, then Pillow-bicubic to R on the
         768 path) and normalised on device from the HBM-resident screenshot (ref:util/utils.py:97-123).
         num_beams: None = `self.num_beams` (default 1, greedy); k > 1 = beam search, the best hypothesis per crop (what
@@ -1665,7 +1914,9 @@ class Florence2Captioner:
         return_scores: None = `self.token_scores` (default False); True returns (ids, token_logprobs) — f32 [n, ids.shape[1] - 1],
         aligned with ids[:, 1:], see `generate(output_scores=True)` and `caption_confidence`; greedy decoding only.
         controls: a `GenerationControls` or a dict of its keys (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
-        suppress_tokens, begin_suppress_tokens, bad_words_ids), see `generate`; None or neutral = the call as it was."""
+        suppress_tokens, begin_suppress_tokens, bad_words_ids), see `generate`; None or neutral = the call as it was.
+        vocabulary: a `CaptionVocabulary` or a list of labels as id lists, see `generate`: every row is one of the labels
+        (`CaptionVocabulary.label_index` names it); greedy decoding without controls only; None = the call as it was."""
         beam = self.beam_config(num_beams)
         scores = self.token_scores if return_scores is None else return_scores
         if not isinstance(scores, bool):
@@ -1674,6 +1925,7 @@ class Florence2Captioner:
             raise ValueError("token scores are a greedy-decoding output (num_beams=1); beam search has none")
         self.check_max_new(max_new_tokens, beam)
         controls = self.generation_controls(controls, max_new_tokens, beam)
+        vocab = self.caption_vocabulary(vocabulary, max_new_tokens, beam, controls)
         prompt = self.prompt_batch([list(prompt_ids)] * len(boxes_px), self.resolution) if prompt_ids is not None and len(boxes_px) else None
         batch_size = max(1, min(int(batch_size), 128))      # plan capacity: buckets stop at 128 crops (the reference's default batch)
 
@@ -1681,7 +1933,7 @@ class Florence2Captioner:
             rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
             self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
         with self._lock:
-            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt, scores, controls)
+            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt, scores, controls, vocab)
         if not parts:
             ids = torch.zeros((0, 1), dtype=torch.long)
             return (ids, torch.zeros((0, 0), dtype=torch.float32)) if scores else ids

@@ -165,6 +165,9 @@ def main():
     ap.add_argument("--caption_generation", type=json.loads, default=None,
                     help="generation controls of the captions as a JSON object, e.g. '{\"repetition_penalty\": 1.3, \"min_new_tokens\": 4}' "
                          "(keys: repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, bad_words_ids)")
+    ap.add_argument("--caption_vocabulary", type=json.loads, default=None,
+                    help="closed set of icon captions as a JSON list of strings (they need the tokenizer.json next to the checkpoint) or of "
+                         "token id lists, e.g. '[\"close\", \"settings\", \"search\"]': every captioned icon gets exactly one of them")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
     a = ap.parse_args()

@@ -83,6 +83,30 @@ class Omniparser(object):
                 raise ValueError(f"caption_generation must be a dict of generation controls or None, got {cg!r}")
             GenerationControls.of(cg)
             self.caption_generation = dict(cg)
+        # caption_vocabulary: a closed set of icon captions — a list of strings (tokenised per call by the caption processor, which
+        # needs the tokenizer.json next to the checkpoint) or of token id lists ([forced BOS] text EOS): every captioned icon's content
+        # is then exactly one of them, picked by one greedy decode on the device (Florence2Captioner.generate(vocabulary=...)).  None
+        # (default) = free text.  Types and limits are checked here, ids against the model by the captioner.  Not together with
+        # caption_generation or caption_num_beams > 1: the captioner refuses both.
+        self.caption_vocabulary = None
+        if config.get("caption_vocabulary") is not None:
+            from ..florence import CaptionVocabulary
+            cv = config["caption_vocabulary"]
+            if not isinstance(cv, (list, tuple)) or not cv:
+                raise ValueError(f"caption_vocabulary must be a non-empty list of strings or token id lists, or None; got {cv!r}")
+            for entry in cv:
+                if isinstance(entry, str):
+                    if not entry.strip():
+                        raise ValueError("caption_vocabulary: an empty string")
+                elif not isinstance(entry, (list, tuple)):
+                    raise ValueError(f"caption_vocabulary: an entry is a string or a list of token ids, got {entry!r}")
+            id_rows = [e for e in cv if not isinstance(e, str)]
+            if id_rows:
+                CaptionVocabulary(id_rows)
+            if self.caption_generation is not None:
+                raise ValueError("caption_vocabulary cannot be combined with caption_generation: a closed vocabulary is decoded without "
+                                 "generation controls")
+            self.caption_vocabulary = list(cv)
 
     def _ocr(self, image: Image.Image, ocr=None):
         """`ocr` = (texts, xyxy px boxes) handed over by the caller for THIS image; else the configured provider."""
@@ -96,7 +120,8 @@ class Omniparser(object):
             image, self.som_model, BOX_TRESHOLD=self.config["BOX_TRESHOLD"], ocr_bbox=boxes, ocr_text=texts,
             draw_bbox_config=overlay_style(image.size), caption_model_processor=self.caption_model_processor, **_SOM_ARGS,
             **({"max_new_tokens": self.caption_max_new_tokens} if self.caption_max_new_tokens != 20 else {}),
-            **({"generation": self.caption_generation} if self.caption_generation is not None else {}))
+            **({"generation": self.caption_generation} if self.caption_generation is not None else {}),
+            **({"caption_vocabulary": self.caption_vocabulary} if self.caption_vocabulary is not None else {}))
         return labeled, elements
 
     def describe(self, image_base64: str, task="<MORE_DETAILED_CAPTION>", max_new_tokens=256, generation=None):

@@ -404,7 +404,7 @@ def crop_boxes_px(ratio_boxes, W, H):
 
 @torch.inference_mode()
 def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_model_processor, prompt=None, batch_size=128,
-                            return_confidence=False, max_new_tokens=None, generation=None):
+                            return_confidence=False, max_new_tokens=None, generation=None, vocabulary=None):
     """ref:util/utils.py:88-132.  Crops are cut/resized/normalised on device and captioned by the HIP
     captioner; `image_source` may be the uint8 HWC numpy image (as in the reference) or a device tensor.
     prompt: the caption prompt of every crop, as the reference's (a Florence-2 task token or free text,
@@ -415,9 +415,18 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
     (`<DETAILED_CAPTION>`, free text) a larger value gives per-icon descriptions; the captioner validates it.
     generation: a dict of generation controls (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens,
     begin_suppress_tokens, bad_words_ids; `Florence2Captioner.generate`) handed to `caption_crops(controls=...)`; None = the call
-    as it was."""
+    as it was.
+    vocabulary: a closed set of captions — a list of strings (tokenised by the processor's `prompt_ids`: they need the tokenizer.json
+    next to the checkpoint, ValueError without it) or of token id lists ([forced BOS] text EOS; always work), handed to
+    `caption_crops(vocabulary=...)`: every caption is then exactly one of them (a string entry comes back as it was given), chosen
+    by ONE greedy decode however many there are, and the confidence is `caption_confidence` of the constrained log-probabilities.
+    With max_new_tokens=None the longest label is generated in full even beyond 20 tokens.  Not together with `generation`.  None =
+    the call as it was."""
     model, processor = caption_model_processor["model"], caption_model_processor["processor"]
+    vocab = caption_vocabulary(vocabulary, processor)
     max_new = 20 if max_new_tokens is None else max_new_tokens
+    if vocab is not None and max_new_tokens is None:
+        max_new = max(max_new, vocab[0].longest)
     non_ocr = filtered_boxes[starting_idx:] if starting_idx else filtered_boxes
     H, W = image_source.shape[0], image_source.shape[1]
     boxes_px = crop_boxes_px(non_ocr.tolist() if isinstance(non_ocr, torch.Tensor) else non_ocr, W, H)
@@ -429,15 +438,51 @@ def get_parsed_content_icon(filtered_boxes, starting_idx, image_source, caption_
     pkw = {} if prompt is None or prompt == "<CAPTION>" else {"prompt_ids": processor.prompt_ids(prompt)}
     if generation is not None:
         pkw["controls"] = generation
+    if vocab is not None:
+        pkw["vocabulary"] = vocab[0]
+
+    def texts_of(ids):
+        texts = [t.strip() for t in processor.batch_decode(ids, skip_special_tokens=True)]
+        if vocab is not None:                # a label given as a string comes back as that string
+            for k, r in enumerate(ids.tolist()):
+                j = vocab[0].label_index(r[1:], model.w.eos)
+                if j >= 0 and vocab[1][j] is not None:
+                    texts[k] = vocab[1][j]
+        return texts
     if return_confidence:                    # only when asked for: captioners without the keyword keep working
         from ..florence import caption_confidence
         ids, logp = model.caption_crops(img_dev, boxes_px, max_new_tokens=max_new, batch_size=batch_size, return_scores=True, **pkw)
-        texts = processor.batch_decode(ids, skip_special_tokens=True)
         w = model.w
-        return [(t.strip(), caption_confidence(r, lp, w.eos, w.forced_bos, w.forced_eos, max_new)) for t, r, lp in zip(texts, ids, logp)]
+        return [(t, caption_confidence(r, lp, w.eos, w.forced_bos, w.forced_eos, max_new)) for t, r, lp in zip(texts_of(ids), ids, logp)]
     ids = model.caption_crops(img_dev, boxes_px, max_new_tokens=max_new, batch_size=batch_size, **pkw)
-    texts = processor.batch_decode(ids, skip_special_tokens=True)
-    return [t.strip() for t in texts]
+    return texts_of(ids)
+
+
+def caption_vocabulary(vocabulary, processor=None):
+    """`vocabulary` of `get_parsed_content_icon` -> None, or (CaptionVocabulary, per distinct label the string it was given as or
+    None).  Entries: strings (tokenised by `processor.prompt_ids`; ValueError without a tokenizer.json) or lists of token ids.
+    ValueError: not a list, an entry of another type, and what `CaptionVocabulary` refuses."""
+    if vocabulary is None:
+        return None
+    from ..florence import CaptionVocabulary
+    if isinstance(vocabulary, CaptionVocabulary):
+        return vocabulary, [None] * len(vocabulary.labels)
+    if isinstance(vocabulary, (str, bytes, dict)) or not hasattr(vocabulary, "__iter__"):
+        raise ValueError(f"a caption vocabulary is a list of strings or of token id lists, got {vocabulary!r}")
+    rows, names = [], {}
+    for entry in vocabulary:
+        if isinstance(entry, str):
+            if processor is None:
+                raise ValueError("a caption vocabulary given as strings needs the caption processor to tokenise it")
+            ids = tuple(int(t) for t in processor.prompt_ids(entry))
+            names.setdefault(ids, entry)
+        elif isinstance(entry, (bytes, dict)) or not hasattr(entry, "__iter__"):
+            raise ValueError(f"caption vocabulary: an entry is a string or a list of token ids, got {entry!r}")
+        else:
+            ids = tuple(entry.tolist() if isinstance(entry, torch.Tensor) else entry)
+        rows.append(ids)
+    vocab = CaptionVocabulary(rows)
+    return vocab, [names.get(lab) for lab in vocab.labels]
 
 
 def _generation_kwargs(generation):
@@ -727,12 +772,14 @@ def annotate_encode_device_batch(frames, boxes_per_frame, phrases_per_frame, **k
 def get_som_labeled_img(image_source: Union[str, Image.Image], model=None, BOX_TRESHOLD=0.01, output_coord_in_ratio=False,
                         ocr_bbox=None, text_scale=0.4, text_padding=5, draw_bbox_config=None, caption_model_processor=None,
                         ocr_text=[], use_local_semantics=True, iou_threshold=0.9, prompt=None, scale_img=False, imgsz=None,
-                        batch_size=128, caption_confidence=False, max_new_tokens=None, generation=None):
+                        batch_size=128, caption_confidence=False, max_new_tokens=None, generation=None, caption_vocabulary=None):
     """ref:util/utils.py:417-496 — returns (base64 PNG, label_coordinates, filtered_boxes_elem).
     caption_confidence (or a caption model with `token_scores` set): every element whose content the captioner wrote gains
     "confidence", see `florence.caption_confidence`; OCR elements and icons that took OCR text have no such key.
     max_new_tokens: tokens generated per captioned icon, None = 20 (`get_parsed_content_icon`).
-    generation: generation controls of the icon captions, None = none (`get_parsed_content_icon`)."""
+    generation: generation controls of the icon captions, None = none (`get_parsed_content_icon`).
+    caption_vocabulary: a closed set of icon captions (strings or token id lists), None = free text (`get_parsed_content_icon`'s
+    `vocabulary`): every captioned icon's content is one of them."""
     if isinstance(image_source, str):
         image_source = Image.open(image_source)
     image_source = image_source.convert("RGB")
@@ -763,7 +810,8 @@ def get_som_labeled_img(image_source: Union[str, Image.Image], model=None, BOX_T
         parsed = get_parsed_content_icon(filtered_boxes, starting_idx, image_np, caption_model_processor, prompt=prompt,
                                          batch_size=batch_size, **({"return_confidence": True} if conf else {}),
                                          **({"max_new_tokens": max_new_tokens} if max_new_tokens is not None else {}),
-                                         **({"generation": generation} if generation is not None else {}))
+                                         **({"generation": generation} if generation is not None else {}),
+                                         **({"vocabulary": caption_vocabulary} if caption_vocabulary is not None else {}))
         for box in elems:
             if box["content"] is None and parsed:
                 if conf:
