@@ -387,6 +387,27 @@ enum {
    * One kernel, greedy_vocab_step_kernel (csrc/vocab_step.hip).  LDS: i3 x 4 bytes + the reduction arrays <= 48 KiB, else
    * OMNI_E_ARG.  Plan bundles and the model-level entry points do not use it. */
   OMNI_OP_GREEDY_VOCAB_STEP = OMNI_OP_GREEDY_CTRL_STEP + 1,   /* 27 (spelled like the kind above: the literally numbered kinds stay 1..24) */
+  /* VISUAL EMBEDDINGS of crops and exemplar matching (csrc/visual_match.hip).  Row 0 of a crop's img_feat — the spatial-average
+   * token behind image_projection and image_proj_norm — is Florence-2's global descriptor of the crop.  i0 selects the mode:
+   *  i0 = 0, embed (embed_rows_kernel, one wave per crop):
+   *    p0 x [i1 rows of i2 elements] of the op's dtype (f32 / f16): the first i3 elements of a row are read   p4 y f32[i1, i3]
+   *    p5 norm f32[i1]        i1 = crops (1..65536)  i2 = row stride in elements (n_img D; % 4 == 0, >= i3)  i3 = D (% 4 == 0, <= 4096)
+   *    y = x / |x| with |x| accumulated in f32; a zero row gives a zero vector and norm 0.  p0 / p4 aligned to 4 elements.
+   *  i0 = 1, partial top-k (match_partial_kernel):
+   *    p0 Q f32[i1, i3] and p1 G f32[i2, i3], unit vectors, 16-byte aligned   p5 partials, 8-byte aligned   i6 = bytes of p5
+   *    i1 = m queries (1..4096)  i2 = n gallery rows (1..65536)  i3 = D (% 4 == 0, <= 4096)  i4 = k (1..8)
+   *    i5 = gallery rows per split, 0 = the launcher's choice (a large gallery fills the chip, a small one is one block per group
+   *    of 8 queries); a value > 0 is the test handle, as the conv op's tile override i22 is.
+   *    Grid (splits, groups of 8 queries).  The score of (q, g) is the f32 dot product in one summation order that depends on D
+   *    alone: the same bits under every i5.  p5 receives {f32 score, i32 gallery index} [m][splits][k], each query's best k of
+   *    each split, -inf / -1 where a split has fewer rows.
+   *  i0 = 2, merge (match_merge_kernel), a second launch with the same i1..i6 and p5:
+   *    p4 idx i32[m, k]   p6 score f32[m, k]: descending score, the lower gallery index first among equals; positions behind
+   *    min(k, n) hold -1 and -inf.
+   * OMNI_E_ARG (nothing launched, nothing written): any value outside its range, a NULL or misaligned pointer, i6 below the
+   * m x splits x k x 8 bytes of the split in force (omni_visual_match_cfg reports them).  The pointer check covers exactly those
+   * extents.  The op's dtype matters to mode 0 only.  Plan bundles and the model-level entry points do not use it. */
+  OMNI_OP_VISUAL_MATCH = OMNI_OP_GREEDY_VOCAB_STEP + 1,   /* 28 (spelled like the two kinds above) */
   OMNI_OP__END
 };
 
@@ -477,6 +498,11 @@ int omni_debug_tile_map(int mtiles, int ntiles, int xcd_n, long long weight_byte
  *   out[4] loader: 0 = generic (ragged K vectors), 1 = aligned, 2 = pointwise, 3 = row-patch (i25)
  *   out[5] split-K count   out[6] 0 = no split-K, 1 = reduce launch, 2 = in-launch combine (i24)   out[7] waves per workgroup */
 int omni_debug_conv_cfg(const omni_op_t* op, int out[8]);
+
+/* The launch geometry of an OMNI_OP_VISUAL_MATCH op of mode 1 or 2, computed by the function the launcher itself calls; no device
+ * work, no pointer of the op is looked at, i6 is not checked.  The op's own argument errors are returned as the launch returns them.
+ *   out[0] groups of 8 queries   out[1] gallery rows per split   out[2] splits   out[3] bytes of the partials buffer (p5) */
+int omni_visual_match_cfg(const omni_op_t* op, long long out[4]);
 
 /* ------------------------------------------------------------------------ *
  * Model-level entry points: the two models of the hot path for hosts

@@ -22,6 +22,7 @@ OP_EMBED_STEP, OP_ATTN_DECODE, OP_GREEDY_STEP, OP_CROP_RESIZE, OP_DWCONV3_LN, OP
 OP_OVERLAY, OP_PNG_PACK, OP_PNG_DEFLATE, OP_MLP_FUSED, OP_BEAM_STEP = 21, 22, 23, 24, 25
 OP_GREEDY_CTRL_STEP = 26
 OP_GREEDY_VOCAB_STEP = 27
+OP_VISUAL_MATCH = 28
 CAND_BYTES = 32
 ABI_VERSION = 3         # include/omni_amd.h::OMNI_ABI_VERSION — a library built from other headers is refused at load time
 
@@ -34,6 +35,7 @@ EXPORTS = [
     "omni_model_load", "omni_model_destroy", "omni_model_int", "omni_model_tensor", "omni_model_run",
     "omni_detector_create", "omni_detector_infer", "omni_captioner_create", "omni_captioner_caption",
     "omni_overflow_count",
+    "omni_visual_match_cfg",
 ]
 
 
@@ -120,6 +122,8 @@ def bind(path):
     L.omni_captioner_caption.restype = c_int
     L.omni_overflow_count.argtypes = [c_int, POINTER(ctypes.c_ulonglong)]
     L.omni_overflow_count.restype = c_int
+    L.omni_visual_match_cfg.argtypes = [POINTER(OmniOp), POINTER(ctypes.c_longlong)]
+    L.omni_visual_match_cfg.restype = c_int
     if L.omni_abi_version() != ABI_VERSION:
         raise OmniError(f"ABI version mismatch: library {L.omni_abi_version()}, host code {ABI_VERSION} (rebuild: python -m omniparser_amd.build)")
     return L

@@ -74,6 +74,7 @@ static int dispatch(const omni_op_t* op, hipStream_t s) {
     case OMNI_OP_PROJ_PREP: case OMNI_OP_ASSEMBLE: case OMNI_OP_EMBED_STEP: case OMNI_OP_GREEDY_STEP:
     case OMNI_OP_BEAM_STEP: case OMNI_OP_GREEDY_CTRL_STEP: case OMNI_OP_CROP_RESIZE: return omni_launch_misc(op, s);
     case OMNI_OP_GREEDY_VOCAB_STEP: return omni_launch_vocab_step(op, s);
+    case OMNI_OP_VISUAL_MATCH: return omni_launch_visual_match(op, s);
     default:
       omni_set_error("unknown op kind %d", op->kind);
       return OMNI_E_ARG;
@@ -167,6 +168,17 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       ext[3] = ext[5] = rows * 4;
       ext[6] = 4;
       ext[7] = i[12];
+      break;
+    }
+    case OMNI_OP_VISUAL_MATCH: {                             // what each mode reads and writes; an op the launcher refuses: first bytes
+      const long long D = i[3];
+      if (i[0] == 0) {                                       // p0 x: the first D elements of i1 rows of stride i2; p4 y; p5 norms
+        ext[0] = i[1] > 0 ? (((long long)i[1] - 1) * i[2] + D) * esz : 1; ext[4] = (long long)i[1] * D * 4; ext[5] = (long long)i[1] * 4;
+      } else if (const long long part = omni_visual_match_part_bytes(op)) {
+        ext[5] = part;
+        if (i[0] == 1) { ext[0] = (long long)i[1] * D * 4; ext[1] = (long long)i[2] * D * 4; }
+        else { ext[4] = ext[6] = (long long)i[1] * i[4] * 4; }
+      }
       break;
     }
     case OMNI_OP_MLP_FUSED: {

@@ -6,6 +6,7 @@ graphs.  Replaces, for `icon_caption`, what the reference reaches through
 loop of hf:generation/utils.py:2783-2937.  Host Python only wires pointers; there is no torch math
 on the path and no CPU fallback.
 """
+import contextlib
 import json
 import math
 import os
@@ -603,6 +604,71 @@ def sequence_score(token_logprobs, lengths, labels=None, normalize="mean", force
     return total / counted.sum(-1).clamp(min=1)
 
 
+# ---- visual embeddings and exemplar matching (OMNI_OP_VISUAL_MATCH, csrc/visual_match.hip)
+MATCH_MAX_K, MATCH_MAX_D, MATCH_MAX_QUERIES, MATCH_MAX_GALLERY = 8, 4096, 4096, 65536      # the op's limits (include/omni_amd.h)
+
+
+def embed_op(dtype, x_ptr, ld, y: torch.Tensor, norm: torch.Tensor, n: int, D: int):
+    """mode 0: the first D elements of n rows of stride `ld` elements at `x_ptr` (the op's dtype) -> unit vectors y f32 [>= n, D]
+    and their norms f32 [>= n]"""
+    return L.make_op(L.OP_VISUAL_MATCH, dtype, p=[x_ptr, None, None, None, y.data_ptr(), norm.data_ptr()], i={0: 0, 1: n, 2: ld, 3: D})
+
+
+def match_ops(q_ptr, g_ptr, part_ptr, idx_ptr, score_ptr, m, n, D, k, split_len=0, part_bytes=0):
+    """(mode 1, mode 2) of one match: the same i-slots, so both see the same split"""
+    i = {1: m, 2: n, 3: D, 4: k, 5: split_len, 6: part_bytes}
+    return (L.make_op(L.OP_VISUAL_MATCH, L.F32, p=[q_ptr, g_ptr, None, None, None, part_ptr], i={0: 1, **i}),
+            L.make_op(L.OP_VISUAL_MATCH, L.F32, p=[None, None, None, None, idx_ptr, part_ptr, score_ptr], i={0: 2, **i}))
+
+
+def match_geometry(m, n, D, k, split_len=0):
+    """(query groups, gallery rows per split, splits, bytes of the partials buffer) of a match, asked of the launcher itself
+    (omni_visual_match_cfg: the function the launch calls; no device work)"""
+    import ctypes
+    out = (ctypes.c_longlong * 4)()
+    L.check(L.lib().omni_visual_match_cfg(ctypes.byref(match_ops(None, None, None, None, None, m, n, D, k, split_len)[0]), out))
+    return tuple(int(v) for v in out)
+
+
+def check_match_args(queries, gallery, top_k):
+    """(m, n, D) of `Florence2Captioner.match`'s arguments, or a ValueError before anything reaches the device"""
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= MATCH_MAX_K:
+        raise ValueError(f"top_k must be an integer in 1..{MATCH_MAX_K}, got {top_k!r}")
+    for name, t in (("queries", queries), ("gallery", gallery)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() < 1:
+            raise ValueError(f"{name} must be an f32 tensor [.., D], got {type(t).__name__}"
+                             + (f" {t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else ""))
+    D = queries.shape[-1]
+    if gallery.shape[-1] != D:
+        raise ValueError(f"queries have D = {D}, the gallery has D = {gallery.shape[-1]}")
+    m, n = (queries.numel() // D if D else 0), (gallery.numel() // D if D else 0)
+    if m < 1 or n < 1:
+        raise ValueError(f"an empty side: {m} queries, {n} gallery rows")
+    if D % 4 or D > MATCH_MAX_D:
+        raise ValueError(f"D = {D}: a multiple of 4 up to {MATCH_MAX_D}")
+    if m > MATCH_MAX_QUERIES or n > MATCH_MAX_GALLERY:
+        raise ValueError(f"{m} queries x {n} gallery rows: at most {MATCH_MAX_QUERIES} x {MATCH_MAX_GALLERY} per call")
+    return m, n, D
+
+
+@torch.inference_mode()
+def match_topk(queries, gallery, top_k=1, device=None):
+    """`Florence2Captioner.match` without a captioner (it needs no weights): both launches go to the CURRENT stream of `device`
+    (default: the queries' device), where the caller's tensors were produced and the results will be read."""
+    m, n, D = check_match_args(queries, gallery, top_k)
+    dev = L.require_device(device if device is not None else (queries.device if queries.is_cuda else None), "match")
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        q = queries.reshape(m, D).to(dev).contiguous()
+        g = gallery.reshape(n, D).to(dev).contiguous()
+        nbytes = match_geometry(m, n, D, top_k)[3]
+        part = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+        idx = torch.empty((m, top_k), dtype=torch.int32, device=dev)
+        score = torch.empty((m, top_k), dtype=torch.float32, device=dev)
+        for op in match_ops(q.data_ptr(), g.data_ptr(), part.data_ptr(), idx.data_ptr(), score.data_ptr(), m, n, D, top_k, 0, nbytes):
+            L.launch(op)
+        return idx.long(), score
+
+
 _DECODE_TUNING = "unset"
 
 
@@ -984,10 +1050,11 @@ class _CaptionPlans(_StepPlans):
     pad token's embedding, attend to the valid keys, stay finite) and are read by nobody."""
 
     def __init__(self, cap: "Florence2Captioner", B: int, R: int, max_new: int, arena: Optional["_CaptionPlans"] = None, stream=None,
-                 beam=None, n_txt=None, scores=False, force=None, controls=False, vocab=False):
+                 beam=None, n_txt=None, scores=False, force=None, controls=False, vocab=False, embed=False):
         w, dev, dt = cap.w, cap.device, cap.dtype
         if arena is not None:
             n_txt = arena.n_txt
+        self.embed = bool(embed)
         self.n_txt = n_txt
         sd = w.sd
         self.B, self.R, self.T = B, R, max_new + 1
@@ -1225,6 +1292,26 @@ class _CaptionPlans(_StepPlans):
         img_feat = pb.alloc(B, n_img, 1, D)
         layernorm(mp + "image_proj_norm", pj, img_feat)
         self.img_feat = img_feat
+        if embed:
+            # ---------------- embed-only plan set: the op list up to here (the same ops in the same buffers as every caption plan of this
+            # capacity), then OMNI_OP_VISUAL_MATCH mode 0 on row 0 of every crop.  No OMNI_OP_ASSEMBLE, no encoder, no cross-K/V, no step plan.
+            assert arena is None and not (beam or force or controls or vocab or scores) and n_txt is None
+            self.emb = pb.raw((B, D), torch.float32)
+            self.emb_norm = pb.raw((B,), torch.float32)
+            pb.add_op(embed_op(dt, img_feat.ptr, n_img * D, self.emb, self.emb_norm, B, D))
+            self.S = self.prompt_ids = self.nkeys = self.step_plan = self.free_evt = None
+            self.cross_kv = []
+            self.n_encode_ops = len(pb.ops)
+            self.encode_flops = pb.flops
+            self.encode_plan = pb.build()
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)         # allocations / uploads ran on the current stream: order them before cap.stream
+            if cap.use_graph:
+                self.encode_plan.run(cap.stream)    # first launches outside a capture
+                cap.stream.synchronize()
+                self.encode_plan.capture(cap.stream)
+                cap.stream.synchronize()
+            return
         # ---------------- encoder
         lm = "model.language_model."
         S = n_img + (len(PROMPT_IDS) if n_txt is None else n_txt)
@@ -1573,6 +1660,13 @@ class Florence2Captioner:
             return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, n_txt=n_txt, scores=scores, vocab=True))
         return self._cached_plan(key, lambda: _CaptionPlans(self, B, R, max_new, beam=beam, n_txt=n_txt, scores=scores))
 
+    @torch.inference_mode()
+    def embed_plans(self, B, R) -> _CaptionPlans:
+        """the embed-only plan set of B crops at resolution R (`_CaptionPlans(embed=True)`): an entry of the plan cache of its own
+        (`embed` is in the key, which no caption plan's key holds), under the same byte-bounded LRU; only ever built by `embed` /
+        `embed_crops`"""
+        return self._cached_plan((B, R, 0, 0, None, "embed"), lambda: _CaptionPlans(self, B, R, 1, embed=True))
+
     def generation_controls(self, controls, max_new_tokens, beam=None) -> Optional[GenerationControls]:
         """`controls` (None, a dict of GEN_CTRL_KEYS or a GenerationControls) checked against this model, before anything touches a
         device: None when they are neutral (the call is the default call), else the checked object.  ValueError: a bad value
@@ -1714,9 +1808,11 @@ class Florence2Captioner:
         return self._dec_stream
 
     # ---- decode loop shared by both entry points
-    def _run(self, cp: _CaptionPlans, n: int, max_new: int, defer: bool = False) -> torch.Tensor:
+    def _run(self, cp: _CaptionPlans, n: int, max_new: int, defer: bool = False, embeds: Optional[list] = None) -> torch.Tensor:
         run = (lambda p: p.replay(self.stream)) if self.use_graph else (lambda p: p.run(self.stream))
         run(cp.encode_plan)
+        if embeds is not None:             # caption_crops(return_embeddings=True): one eager launch behind the encode plan, same stream
+            embeds.append(self._embed_rows(cp, n))
         poll = 0 if defer else self.early_exit_every
         steps = 0
         for t in range(max_new):
@@ -1846,7 +1942,17 @@ class Florence2Captioner:
         rows = [r for p in parts for r in (p[0] if scores else p)[:, 1:].tolist()]
         return torch.tensor([vocab.label_index(r, self.w.eos) for r in rows], dtype=torch.long)
 
-    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False, controls=None, vocab=None):
+    def _embed_rows(self, cp: _CaptionPlans, n: int) -> torch.Tensor:
+        """f32 [n, D] on the device: OMNI_OP_VISUAL_MATCH mode 0 on row 0 of the first n crops of `cp.img_feat`, launched eagerly on
+        the captioner's stream behind the encode plan that wrote it (img_feat is never released to another tensor of the plan)"""
+        D = self.w.d_model
+        out = torch.empty((n, D), dtype=torch.float32, device=self.device)
+        norm = torch.empty((n,), dtype=torch.float32, device=self.device)
+        L.launch(embed_op(self.dtype, cp.img_feat.ptr, cp.n_img * D, out, norm, n, D), self.stream)
+        return out
+
+    def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False, controls=None, vocab=None,
+                        embeds=None):
         """encode + decode n_all images in chunks of `chunk` on the captioner's stream, each on the plan of its bucket: fill(cp, s, n)
         writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  prompt: `prompt_batch`
         of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results` (scores: plans that
@@ -1873,8 +1979,67 @@ class Florence2Captioner:
                 fill(cp, s, n)
                 if prompt:
                     cp.set_prompt(prompt[0][s:s + n].to(self.device, non_blocking=True), prompt[1][s:s + n].to(self.device, non_blocking=True), n)
-                parts.append(self._run(cp, n, max_new_tokens))
+                parts.append(self._run(cp, n, max_new_tokens, **({"embeds": embeds} if embeds is not None else {})))
         return parts
+
+    def _embed_chunks(self, src, n_all, chunk, R, fill) -> torch.Tensor:
+        """f32 [n_all, D] on the device: the embed-only plan of each chunk's bucket on the captioner's stream, chunked as
+        `_caption_chunks` chunks; fill(cp, s, n) as there"""
+        D = self.w.d_model
+        out = torch.empty((n_all, D), dtype=torch.float32, device=self.device)
+        if self.device.type == "cuda":                      # `out` comes from the caller's stream, as pixels / a screenshot may
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            out.record_stream(self.stream)
+        for s in range(0, n_all, chunk):
+            n = min(chunk, n_all - s)
+            cp = self.embed_plans(self.bucket(n), R)
+            with torch.cuda.stream(self.stream):
+                fill(cp, s, n)
+                (cp.encode_plan.replay if self.use_graph else cp.encode_plan.run)(self.stream)
+                out[s:s + n].copy_(cp.emb[:n], non_blocking=True)
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)     # the caller reads `out` on its own stream
+        return out
+
+    @torch.inference_mode()
+    def embed(self, pixel_values) -> torch.Tensor:
+        """Visual embeddings of images: f32 [n, d_model] on the device, unit length.  pixel_values [n, 3, R, R] as `generate` takes
+        them.  A row is Florence-2's own global descriptor of the image — row 0 of the image features, the spatial-average token
+        behind image_projection and image_proj_norm (transformers' get_image_features(...).pooler_output[:, 0]) — L2-normalised by
+        OMNI_OP_VISUAL_MATCH mode 0.  It is a pure function of the pixels: nothing is cached.  It runs the DaViT tower and the
+        projector only (the embed-only plan of `embed_plans`: no encoder, no cross-K/V, no decode step), in chunks of 128 on the
+        bucket ladder exactly as `generate` chunks."""
+        with self._lock:
+            Bn, _, R, R2 = pixel_values.shape
+            assert R == R2
+
+            def fill(cp, s, n):
+                cp.x_in.t[:n, :, :, :3] = pixel_values[s:s + n].to(self.device).permute(0, 2, 3, 1).to(cp.x_in.t.dtype)
+            return self._embed_chunks(pixel_values, Bn, 128, R, fill)
+
+    @torch.inference_mode()
+    def embed_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], batch_size=128) -> torch.Tensor:
+        """`embed` through the device crop path of `caption_crops`: the rectangles `boxes_px` of the HWC uint8 frame on the device
+        are cut, resized and normalised there.  f32 [len(boxes_px), d_model] on the device."""
+        batch_size = max(1, min(int(batch_size), 128))
+
+        def fill(cp, s, n):
+            rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
+            self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
+        with self._lock:
+            return self._embed_chunks(image_u8, len(boxes_px), batch_size, self.resolution, fill)
+
+    @torch.inference_mode()
+    def match(self, queries: torch.Tensor, gallery: torch.Tensor, top_k=1):
+        """The best `top_k` gallery rows of every query by cosine similarity: (idx i64 [m, top_k], score f32 [m, top_k]) on the
+        device.  queries f32 [.., D] and gallery f32 [.., D] are unit vectors on the device (what `embed` returns); the score is
+        their f32 dot product, whose bits for a pair do not depend on what else is in the call.  Descending score, the lower
+        gallery index first among equals; behind min(top_k, n) positions hold -1 and -inf.  Two launches of OMNI_OP_VISUAL_MATCH
+        (per-slice top-k, merge).  ValueError before anything reaches the device: top_k no int in 1..8, mismatching D, an empty side,
+        D no multiple of 4 or above 4096, more than 4096 queries or 65536 gallery rows."""
+        check_match_args(queries, gallery, top_k)
+        with self._lock:
+            return match_topk(queries, gallery, top_k, self.device)
 
     def _results(self, parts, beam, nrs=1):
         """(sequences, sequences_scores) of the per-chunk `_run` results: beam search as `_beam_outputs`; greedy decoding (scores
@@ -1905,7 +2070,7 @@ class Florence2Captioner:
 
     @torch.inference_mode()
     def caption_crops(self, image_u8: torch.Tensor, boxes_px: List[List[int]], max_new_tokens=20, batch_size=128, num_beams=None,
-                      prompt_ids=None, return_scores=None, controls=None, vocabulary=None):
+                      prompt_ids=None, return_scores=None, controls=None, vocabulary=None, return_embeddings=False):
         """Fused fast path: crops are cut, resized (cv2-bilinear 64x64, then Pillow-bicubic to R on the
         768 path) and normalised on device from the HBM-resident screenshot (ref:util/utils.py:97-123).
         num_beams: None = `self.num_beams` (default 1, greedy); k > 1 = beam search, the best hypothesis per crop (what
@@ -1916,7 +2081,15 @@ class Florence2Captioner:
         controls: a `GenerationControls` or a dict of its keys (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
         suppress_tokens, begin_suppress_tokens, bad_words_ids), see `generate`; None or neutral = the call as it was.
         vocabulary: a `CaptionVocabulary` or a list of labels as id lists, see `generate`: every row is one of the labels
-        (`CaptionVocabulary.label_index` names it); greedy decoding without controls only; None = the call as it was."""
+        (`CaptionVocabulary.label_index` names it); greedy decoding without controls only; None = the call as it was.
+        return_embeddings: True appends the crops' visual embeddings (f32 [n, d_model] on the device, what `embed_crops` returns
+        for the same boxes) to the result: (ids, embeddings), or (ids, token_logprobs, embeddings) with scores.  They are read off
+        the caption plan's own image features by one eager OMNI_OP_VISUAL_MATCH launch behind each chunk's encode plan — one
+        encode, not two; the captured graphs are what they were.  Any decoding mode (img_feat does not depend on it).  False
+        (default) = the call as it was."""
+        if not isinstance(return_embeddings, bool):
+            raise ValueError(f"return_embeddings must be a bool, got {return_embeddings!r}")
+        embeds = [] if return_embeddings else None
         beam = self.beam_config(num_beams)
         scores = self.token_scores if return_scores is None else return_scores
         if not isinstance(scores, bool):
@@ -1933,13 +2106,19 @@ class Florence2Captioner:
             rects = torch.tensor(boxes_px[s:s + n], dtype=torch.int32).to(self.device, non_blocking=True)
             self.launch_crops(cp, 0, n, image_u8, rects, *self.crop_scratch(n, cp.R), self.stream)
         with self._lock:
-            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt, scores, controls, vocab)
+            parts = self._caption_chunks(image_u8, len(boxes_px), batch_size, self.resolution, max_new_tokens, beam, fill, prompt, scores, controls, vocab,
+                                         **({"embeds": embeds} if return_embeddings else {}))
+        emb = ()
+        if return_embeddings:
+            emb = (torch.cat(embeds) if embeds else torch.zeros((0, self.w.d_model), dtype=torch.float32, device=self.device),)
         if not parts:
             ids = torch.zeros((0, 1), dtype=torch.long)
-            return (ids, torch.zeros((0, 0), dtype=torch.float32)) if scores else ids
-        if scores:
-            return self._results_scores(parts)
-        return self._results(parts, beam)[0]
+            out = (ids, torch.zeros((0, 0), dtype=torch.float32)) if scores else (ids,)
+        elif scores:
+            out = self._results_scores(parts)
+        else:
+            out = (self._results(parts, beam)[0],)
+        return out[0] if len(out + emb) == 1 else tuple(out) + emb
 
     # ---- teacher-forced scoring of given texts (OMNI_OP_GREEDY_STEP p5)
     def _check_labels(self, labels, n):

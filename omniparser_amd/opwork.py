@@ -9,7 +9,7 @@ Slot meanings: include/omni_amd.h."""
 NAMES = {1: "conv_igemm/conv_split", 2: "avgpool2", 3: "maxpool", 4: "resize_nearest", 5: "letterbox", 6: "detect_decode", 7: "nms",
          8: "dwconv3", 9: "layernorm", 10: "attn_rows (window / MHA)", 11: "chan_attn", 12: "proj_prep", 13: "assemble", 14: "embed_step",
          15: "attn_decode", 16: "greedy_step", 17: "crop_resize", 18: "dwconv3_ln", 19: "split_convert", 20: "hand_off", 21: "overlay",
-         22: "png_pack", 23: "png_deflate", 24: "mlp_fused", 26: "greedy_ctrl_step"}
+         22: "png_pack", 23: "png_deflate", 24: "mlp_fused", 26: "greedy_ctrl_step", 28: "visual_match"}
 
 MFMA_KINDS = (1, 24, 10)          # priced against the dense f16 MFMA peak; everything else against HBM
 
@@ -55,6 +55,16 @@ def op_work(op, esz=4):
         return 4 * B * heads * nk * 64, esz * B * nk * i[9] * 2
     if k in (16, 26):
         return 0, esz * i[0] * i[1]
+    if k == 28:                                     # i0: 0 = embed (row 0 of every crop in, unit vector + norm out), 1 = partial top-k, 2 = merge
+        if i[0] == 0:
+            n, D = i[1], i[3]
+            return 3 * n * D, n * D * (esz + 4) + 4 * n
+        m, n, D, kk = i[1], i[2], i[3], i[4]
+        ln = i[5] if i[5] > 0 else None             # (the launcher's split: one partial list per query and split; unknown here = 1 split)
+        splits = (n + ln - 1) // ln if ln else 1
+        if i[0] == 1:                               # queries and gallery once (a perfectly cached execution), the partials out
+            return 2 * m * n * D, 4 * (m + n) * D + 8 * m * splits * kk
+        return 0, 8 * m * splits * kk + 8 * m * kk
     return 0, 0
 
 
@@ -75,6 +85,8 @@ def op_shape(op):
         return (i[0] * i[1], i[3], (2 if i[9] == 1 else 1) if i[8] == 1 else 0)
     if k == 15:
         return (i[10], i[9], i[7] if i[7] > 0 else i[8])
+    if k == 28:                                     # embed: (crops, D, 0); match: (queries, D, gallery rows)
+        return (i[1], i[3], 0 if i[0] == 0 else i[2])
     return (i[0], i[3], 0)
 
 
@@ -88,4 +100,6 @@ def op_kernel(op):
         return "gemm_dma" if op.i[20] == 2 else ("conv_split" if op.i[20] else "conv_igemm")
     if op.kind == 11 and op.i[8] == 1:
         return "chan_attn (fold)" if op.i[9] == 1 else "chan_attn (scores + fold)"
+    if op.kind == 28:
+        return ("visual_match (embed)", "visual_match (partial top-k)", "visual_match (merge)")[op.i[0]] if 0 <= op.i[0] <= 2 else "visual_match"
     return NAMES.get(op.kind, str(op.kind))

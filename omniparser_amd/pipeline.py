@@ -292,6 +292,22 @@ class ScreenParser:
         `parse_batch`) by descending likelihood of the query as their crop's text, [{"index", "score"}]"""
         return U.rank_elements(frame, elements, {"model": self.cap, "processor": self.proc}, queries, top_k=top_k)
 
+    def embed(self, frame: torch.Tensor, elements):
+        """`util.utils.embed_elements` for a frame already on the device: (index, unit embeddings f32 [len(index), d_model] on the
+        device) of one frame's elements (its list from `parse_batch`).  A call of its own beside `parse_batch` / `parse_stream`,
+        whose results and wire format do not carry embeddings."""
+        return U.embed_elements(frame, elements, {"model": self.cap, "processor": self.proc})
+
+    def match(self, frame: torch.Tensor, elements, exemplars, top_k=5):
+        """`util.utils.match_elements` for a frame already on the device: per exemplar (images, or an f32 [m, D] tensor of
+        embeddings) the elements that look like it, [{"index", "score"}] by descending cosine similarity"""
+        return U.match_elements(frame, elements, {"model": self.cap, "processor": self.proc}, exemplars, top_k=top_k)
+
+    def track(self, prev_frame: torch.Tensor, prev_elements, frame: torch.Tensor, elements, min_score=0.9):
+        """`util.utils.track_elements` of two frames already on the device: [(prev_index, index, score)], the one-to-one mutual
+        best matches between the elements of the previous frame and of this one"""
+        return U.track_elements(self.embed(prev_frame, prev_elements), self.embed(frame, elements), min_score=min_score)
+
     def prompt_ids(self, prompt):
         """one caption prompt for a call: None (the default <CAPTION> prompt), text (a Florence-2 task token or free text, tokenised
         by the parser's processor) or a list of token ids (bos ... eos) -> list of ids, or None"""

@@ -144,6 +144,18 @@ class Omniparser(object):
         rankings = U.rank_elements(np.asarray(image.convert("RGB")), elements, self.caption_model_processor, queries, top_k=top_k)
         return elements, rankings
 
+    def find_similar(self, image_base64: str, exemplars_base64, top_k=5):
+        """`parse`, then `utils.match_elements` of the parsed elements against exemplar images (base64, as the screenshot is):
+        (parsed_content_list, per exemplar the top_k elements as {"index", "score"} by descending cosine similarity of the caption
+        model's visual embeddings).  The sibling of `ground`: that one asks with a text, this one with a picture."""
+        if isinstance(exemplars_base64, (str, bytes)):
+            raise ValueError("exemplars_base64 is a list of base64 images")
+        image = decode_image(image_base64)
+        exemplars = [np.asarray(decode_image(b).convert("RGB")) for b in exemplars_base64]
+        _labeled, elements = self.parse_image(image)
+        matches = U.match_elements(np.asarray(image.convert("RGB")), elements, self.caption_model_processor, exemplars, top_k=top_k)
+        return elements, matches
+
     def parse_many(self, images_base64: Sequence[str]):
         """Service helper: parse several screenshots with the same models (sequentially; the batched device path
         for equally sized frames is `omniparser_amd.pipeline.ScreenParser.parse_batch`)."""

@@ -572,6 +572,114 @@ def rank_elements(image_source, elements, caption_model_processor, queries, top_
     return ranked
 
 
+def _frame_on(image_source, device):
+    img = image_source if isinstance(image_source, torch.Tensor) else torch.from_numpy(np.array(image_source, order="C"))
+    return img.to(device)
+
+
+@torch.inference_mode()
+def embed_elements(image_source, elements, caption_model_processor):
+    """Visual embeddings of the elements of a screenshot ("which element looks like this one?"): `Florence2Captioner.embed_crops`
+    — the DaViT tower and the projector per crop, no encoder and no decode.
+    image_source: the uint8 HWC numpy image or a device tensor; elements: a `parsed_content_list` with ratio bboxes, of any element
+    type.  Crops are cut as `crop_boxes_px` cuts them; elements whose crop is empty are skipped.
+    -> (index, embeddings): positions in `elements` (as `rank_elements` reports them) and f32 [len(index), d_model] unit vectors
+    on the device, a pure function of each crop's pixels."""
+    model = caption_model_processor["model"]
+    H, W = image_source.shape[0], image_source.shape[1]
+    index, boxes_px = [], []
+    for k, e in enumerate(elements):
+        px = crop_boxes_px([e["bbox"]], W, H)
+        if px:
+            index.append(k)
+            boxes_px.append(px[0])
+    return index, model.embed_crops(_frame_on(image_source, model.device), boxes_px)
+
+
+@torch.inference_mode()
+def embed_exemplars(exemplars, caption_model_processor):
+    """f32 [m, d_model] on the device: `exemplars` as it is when it is such a tensor of embeddings, else one embedding per image
+    (HWC uint8 arrays or PIL images), each through the 64x64 bilinear step and the resize to the captioner's resolution that a crop
+    of the image's full rectangle takes (`embed_crops` of [0, 0, W, H])."""
+    model = caption_model_processor["model"]
+    if isinstance(exemplars, torch.Tensor):
+        if exemplars.dtype != torch.float32 or exemplars.dim() != 2:
+            raise ValueError(f"exemplar embeddings are an f32 [m, D] tensor, got {exemplars.dtype} {tuple(exemplars.shape)}")
+        return exemplars.to(model.device)
+    if isinstance(exemplars, (str, bytes, dict, np.ndarray)) or not hasattr(exemplars, "__iter__"):
+        raise ValueError("exemplars are a list of images (HWC uint8 arrays or PIL images) or an f32 [m, D] tensor of embeddings")
+    rows = []
+    for ex in exemplars:
+        arr = np.array(ex.convert("RGB") if isinstance(ex, Image.Image) else ex, order="C")
+        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3 or not arr.shape[0] or not arr.shape[1]:
+            raise ValueError(f"an exemplar image is HWC uint8 with 3 channels, got {arr.dtype} {arr.shape}")
+        rows.append(model.embed_crops(torch.from_numpy(arr).to(model.device), [[0, 0, arr.shape[1], arr.shape[0]]]))
+    if not rows:
+        raise ValueError("no exemplars: at least one is needed")
+    return torch.cat(rows)
+
+
+def _match_lists(index, idx, score, min_score):
+    """device (idx, score) of a match against the embeddings of `index` -> per query [{"index", "score"}], cut at min_score"""
+    out = []
+    for irow, srow in zip(idx.tolist(), score.tolist()):
+        out.append([{"index": index[i], "score": s} for i, s in zip(irow, srow) if i >= 0 and (min_score is None or s >= min_score)])
+    return out
+
+
+@torch.inference_mode()
+def match_elements(image_source, elements, caption_model_processor, exemplars, top_k=5, min_score=None):
+    """Find by exemplar: which elements of the screenshot look like these images?  `embed_elements`, `embed_exemplars` and
+    `Florence2Captioner.match` (cosine similarity of the embeddings, top-k on the device).
+    exemplars: a list of images or an f32 [m, D] tensor of embeddings (`embed_exemplars`); top_k: 1..8; min_score: drop matches
+    below this similarity (None = keep all).
+    -> per exemplar a list of {"index": position in `elements`, "score"} by descending score (ties: the lower index), at most top_k."""
+    from ..florence import check_match_args
+    model = caption_model_processor["model"]
+    if min_score is not None and (isinstance(min_score, bool) or not isinstance(min_score, (int, float))):
+        raise ValueError(f"min_score must be a number or None, got {min_score!r}")
+    if isinstance(exemplars, torch.Tensor):
+        check_match_args(exemplars, exemplars, top_k)
+    index, emb = embed_elements(image_source, elements, caption_model_processor)
+    queries = embed_exemplars(exemplars, caption_model_processor)
+    if not index:
+        check_match_args(queries, queries, top_k)
+        return [[] for _ in range(queries.shape[0])]
+    idx, score = model.match(queries, emb, top_k=top_k)
+    return _match_lists(index, idx, score, min_score)
+
+
+@torch.inference_mode()
+def track_elements(prev, cur, min_score=0.9, top_k=4):
+    """Track across screenshots: which element of `cur` is which element of `prev`?  prev, cur: (index, embeddings) pairs as
+    `embed_elements` returns them.  Both directions' top_k come from the device (`florence.match_topk`); the filter runs on the
+    host: a pair is a candidate when each side is among the other's top_k with a score of at least min_score, and candidates are
+    accepted by descending score (ties: the lower prev index, then the lower cur index) while both sides are still free — every
+    accepted pair is the mutual best among the elements still unpaired, each element is paired at most once.
+    -> [(prev_index, cur_index, score)] by ascending prev_index."""
+    from ..florence import match_topk
+    (pi, pe), (ci, ce) = prev, cur
+    if isinstance(min_score, bool) or not isinstance(min_score, (int, float)):
+        raise ValueError(f"min_score must be a number, got {min_score!r}")
+    if len(pi) != pe.shape[0] or len(ci) != ce.shape[0]:
+        raise ValueError("an (index, embeddings) pair whose index and embeddings differ in length")
+    if not len(pi) or not len(ci):
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= 8:
+            raise ValueError(f"top_k must be an integer in 1..8, got {top_k!r}")
+        return []
+    fi, fs = match_topk(pe, ce, top_k)
+    bi, _ = match_topk(ce, pe, top_k, fi.device)
+    fi, fs, bi = fi.tolist(), fs.tolist(), bi.tolist()
+    cand = sorted((-s, pi[a], ci[b], a, b) for a in range(len(pi)) for b, s in zip(fi[a], fs[a])
+                  if b >= 0 and s >= min_score and a in bi[b])
+    used_a, used_b, out = set(), set(), []
+    for neg, ia, ib, a, b in cand:
+        if a not in used_a and b not in used_b:
+            used_a.add(a); used_b.add(b)
+            out.append((ia, ib, -neg))
+    return sorted(out)
+
+
 def _box_convert_xyxy_to_cxcywh(b: torch.Tensor) -> torch.Tensor:
     x1, y1, x2, y2 = b.unbind(-1)
     return torch.stack(((x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1), -1)
