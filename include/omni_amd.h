@@ -408,8 +408,44 @@ enum {
    * m x splits x k x 8 bytes of the split in force (omni_visual_match_cfg reports them).  The pointer check covers exactly those
    * extents.  The op's dtype matters to mode 0 only.  Plan bundles and the model-level entry points do not use it. */
   OMNI_OP_VISUAL_MATCH = OMNI_OP_GREEDY_VOCAB_STEP + 1,   /* 28 (spelled like the two kinds above) */
+  /* REGION OCR: Florence-2's <OCR_WITH_REGION> task over native-resolution tiles of a screenshot (csrc/region_ocr.hip).  i0 selects
+   * the mode:
+   *  i0 = 0, tile cut (tile_cut_kernel, one work-item per tile pixel):
+   *    p0 frame u8[i2, i3, 3] (H, W)   p1 origins i32[i1, 2] {x, y} of the tiles' top-left pixels in the frame, any sign
+   *    p4 y [i1][i4][i4][i13] of the op's dtype (f32 / f16): a caption plan's input, the layout, pitch and zeroed padding channels
+   *    OMNI_OP_CROP_RESIZE writes   p7 f32[256], f32(f64(u8) * (1/255))   f0..f2 mean, f3..f5 std (not 0)
+   *    i1 = tiles (1..65536)  i4 = R (1..65536)  i13 = elements per pixel (3..64)
+   *    y = (p7[u8] - mean) / std in f32, stored in the op's dtype: the image processor with do_resize = False.  A tile pixel outside
+   *    the frame takes u8 255 on all channels first (the tile pasted on a white canvas); the frame is never read outside.
+   *  i0 = 1, region parse (region_parse_kernel, one 64-lane block per row):
+   *    p0 ids i32[i1 rows, stride i5 (0 = i2)]: column 0 the decoder start token, then the generated tokens   i2 = T (2..2049)
+   *    p1 class table u16[i4]: 0..999 = location bin, OMNI_OCR_CLASS_STRIP (<s>, </s>, <pad>: deleted before matching),
+   *    OMNI_OCR_CLASS_TEXT, OMNI_OCR_CLASS_HARD (decoded text empty or holding a newline or '<'); larger values and ids outside
+   *    0..i4-1 count as HARD   p2 logp f32[i1 rows, stride i6 (0 = i2 - 1)] aligned with ids[1:], or NULL
+   *    p7 cells i32[i1, 6] per row {origin x, origin y, lo x, hi x, lo y, hi y}: the tile's origin in the frame and the cell it owns
+   *    in DOUBLED frame pixels, lo inclusive, hi exclusive, INT_MAX = no upper end (origins within +-2^30)
+   *    i3 = M, region slots per row: exactly (T - 1) / 9   i7 = R (1..65536)   i8 = the EOS id
+   *    A row is columns 1 .. in front of the first EOS behind column 0 (all of them without one); nothing behind reaches an output.
+   *    On its non-STRIP tokens, from p = 0: e = the smallest index >= p + 1 whose tokens e .. e + 7 are all location bins; region =
+   *    content [p, e) (it may hold stray location tokens) + the eight bins; p = e + 8; until no e exists.  Corner q of a region is
+   *    ((2 bin + 1) R) / 2000 + origin (x for even q, y for odd q).
+   *    p4 records i32[i1 x M, 16], region k of row r at slot r M + k: {r, first and one-past-last ORIGINAL column of the content's
+   *    non-STRIP tokens, x0 y0 .. x3 y3 in frame pixels, n = non-STRIP tokens of content + 8, kept, 0, 0, 0}; kept = the doubled
+   *    centre (min + max over the four corners, per axis) lies in the row's cell on both axes.  Unused slots are zero.
+   *    p5 sums f32[i1 x M]: logp over exactly those n tokens, added in ascending column order (0 with p2 = NULL and in unused slots)
+   *    p6 rows i32[i1, 4] {regions found, regions kept, flags, 0}; flags bit 0 = the row holds a HARD token (the host re-parses
+   *    it from text), bit 1 = no EOS in the generated part (cut off at max_new_tokens).
+   * OMNI_E_ARG (nothing launched, nothing written): any value outside its range, M != (T - 1) / 9, a NULL pointer other than p2, a
+   * misaligned pointer.  The pointer check covers exactly these extents.  The op's dtype matters to mode 0 only.  Plan bundles and
+   * the model-level entry points do not use it. */
+  OMNI_OP_REGION_OCR = OMNI_OP_VISUAL_MATCH + 1,   /* 29 (spelled like the three kinds above) */
   OMNI_OP__END
 };
+
+/* token classes of OMNI_OP_REGION_OCR's class table (p1) above the location bins 0..999 */
+#define OMNI_OCR_CLASS_STRIP 1000
+#define OMNI_OCR_CLASS_TEXT 1001
+#define OMNI_OCR_CLASS_HARD 1002
 
 /* header of the trie block of OMNI_OP_GREEDY_VOCAB_STEP (p7); first / edge_tok / edge_dst follow it, see the op */
 #define OMNI_VOCAB_HEADER_BYTES 32

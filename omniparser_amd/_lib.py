@@ -23,6 +23,8 @@ OP_OVERLAY, OP_PNG_PACK, OP_PNG_DEFLATE, OP_MLP_FUSED, OP_BEAM_STEP = 21, 22, 23
 OP_GREEDY_CTRL_STEP = 26
 OP_GREEDY_VOCAB_STEP = 27
 OP_VISUAL_MATCH = 28
+OP_REGION_OCR = 29
+OCR_CLASS_STRIP, OCR_CLASS_TEXT, OCR_CLASS_HARD = 1000, 1001, 1002      # include/omni_amd.h::OMNI_OCR_CLASS_*
 CAND_BYTES = 32
 ABI_VERSION = 3         # include/omni_amd.h::OMNI_ABI_VERSION — a library built from other headers is refused at load time
 

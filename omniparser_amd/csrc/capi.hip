@@ -75,6 +75,7 @@ static int dispatch(const omni_op_t* op, hipStream_t s) {
     case OMNI_OP_BEAM_STEP: case OMNI_OP_GREEDY_CTRL_STEP: case OMNI_OP_CROP_RESIZE: return omni_launch_misc(op, s);
     case OMNI_OP_GREEDY_VOCAB_STEP: return omni_launch_vocab_step(op, s);
     case OMNI_OP_VISUAL_MATCH: return omni_launch_visual_match(op, s);
+    case OMNI_OP_REGION_OCR: return omni_launch_region_ocr(op, s);
     default:
       omni_set_error("unknown op kind %d", op->kind);
       return OMNI_E_ARG;
@@ -181,6 +182,15 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       }
       break;
     }
+    case OMNI_OP_REGION_OCR:                                 // what each mode reads and writes; an op the launcher refuses: first bytes
+      if (i[0] == 0) {                                       // p0 frame, p1 origins, p4 the tiles, p7 the 1/255 table
+        if (i[1] > 0 && i[2] > 0 && i[3] > 0 && i[4] > 0 && i[13] > 0) {
+          ext[0] = (long long)i[2] * i[3] * 3; ext[1] = (long long)i[1] * 8; ext[4] = (long long)i[1] * i[4] * i[4] * i[13] * esz; ext[7] = 1024;
+        }
+      } else if (i[0] == 1) {
+        omni_region_ocr_extents(op, ext);
+      }
+      break;
     case OMNI_OP_MLP_FUSED: {
       const long long rows = (long long)i[0] * i[1], C = i[3], hid = i[12];
       ext[0] = span(rows, i[4], i[5], C); ext[1] = hid * C * 4; ext[2] = hid * 4; ext[3] = span(rows, i[16], i[17], C);

@@ -224,6 +224,8 @@ int omni_launch_misc(const omni_op_t* op, hipStream_t s);
 int omni_launch_vocab_step(const omni_op_t* op, hipStream_t s);
 int omni_launch_visual_match(const omni_op_t* op, hipStream_t s);
 long long omni_visual_match_part_bytes(const omni_op_t* op);
+int omni_launch_region_ocr(const omni_op_t* op, hipStream_t s);
+bool omni_region_ocr_extents(const omni_op_t* op, long long ext[8]);
 int omni_launch_glue(const omni_op_t* op, hipStream_t s);
 int omni_launch_overlay(const omni_op_t* op, hipStream_t s);
 int omni_launch_png_pack(const omni_op_t* op, hipStream_t s);

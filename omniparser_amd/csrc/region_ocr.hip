@@ -1,0 +1,222 @@
+// OMNI_OP_REGION_OCR: Florence-2's <OCR_WITH_REGION> task over native-resolution tiles of a screenshot.  Two modes (i0), see
+// include/omni_amd.h:
+//
+//   0 tile cut      n windows of R x R pixels of the HBM-resident u8 [H, W, 3] frame, at origins read from a device table, rescaled
+//                   and normalised into a caption plan's input exactly as the image processor does without its resize; a pixel
+//                   outside the frame is white (u8 255) before normalisation.  One work-item per tile pixel.
+//   1 region parse  one 64-lane block per row of generated ids: the answer "text <loc>x8 text <loc>x8 ..." is cut into regions,
+//                   the location bins are de-quantised to frame pixels, every region gets the sum of its tokens'
+//                   log-probabilities and a flag saying whether its own tile owns it.  Token classes come from a table in device
+//                   memory, so the kernel knows no tokenizer.
+//
+// Mode 1 works on the row with its STRIP tokens taken out, which is what transformers does to the decoded text before it applies its
+// pattern `(.+?)(<loc_n>){8}`: from p = 0, e is the smallest index >= p + 1 whose eight tokens e .. e + 7 are all location tokens; the
+// region's content is [p, e), then p = e + 8.  The walk is a dependent chain, so lane 0 makes it over the classes staged in LDS
+// (every lane classifies and stages them first); the regions it finds are then finished one lane per region, each with a plain
+// sequential f32 sum in ascending token order — the bits do not depend on the launch geometry, and a host twin repeats them.
+// Column 0 of a row is the decoder start token and never part of the answer; the row ends in front of the first EOS behind it, and
+// nothing behind that EOS reaches an output.
+#include "omni_internal.h"
+
+#include <limits.h>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kMaxTiles = 65536, kMaxR = 65536, kMaxT = 2049, kMaxM = (kMaxT - 1) / 9;
+constexpr int kStrip = OMNI_OCR_CLASS_STRIP, kHard = OMNI_OCR_CLASS_HARD;      // 0..999: the location bin itself
+
+// ---------------------------------------------------------------------------------------------- mode 0
+struct CutArgs {
+  const unsigned char* img; const int* origins; void* y; const float* lut;
+  int n, H, W, R, ldo; float mean[3], stdv[3];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void tile_cut_kernel(CutArgs a) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int tile = blockIdx.y;
+  if (idx >= (long long)a.R * a.R) return;
+  const int yy = (int)(idx / a.R), xx = (int)(idx - (long long)yy * a.R);
+  const long long sx = (long long)a.origins[tile * 2] + xx, sy = (long long)a.origins[tile * 2 + 1] + yy;
+  int p[3] = {255, 255, 255};                                // outside the frame: the white canvas the tile is pasted on
+  if (sx >= 0 && sx < a.W && sy >= 0 && sy < a.H) {
+    const unsigned char* s = a.img + (sy * a.W + sx) * 3;
+    p[0] = s[0]; p[1] = s[1]; p[2] = s[2];
+  }
+  T* out = (T*)a.y + ((long long)tile * a.R * a.R + idx) * a.ldo;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v = a.lut[p[c]];                             // f32(f64(p) * (1/255)), the table OMNI_OP_CROP_RESIZE reads
+    out[c] = ElemTraits<T>::from_f32((v - a.mean[c]) / a.stdv[c]);
+  }
+  for (int c = 3; c < a.ldo; ++c) out[c] = ElemTraits<T>::from_f32(0.0f);
+}
+
+int launch_cut(const omni_op_t* op, hipStream_t s) {
+  CutArgs a{};
+  a.img = (const unsigned char*)op->p[0]; a.origins = (const int*)op->p[1]; a.y = op->p[4]; a.lut = (const float*)op->p[7];
+  a.n = op->i[1]; a.H = op->i[2]; a.W = op->i[3]; a.R = op->i[4]; a.ldo = op->i[13];
+  for (int c = 0; c < 3; ++c) { a.mean[c] = op->f[c]; a.stdv[c] = op->f[3 + c]; }
+  OMNI_REQUIRE(a.n >= 1 && a.n <= kMaxTiles, "region_ocr cut: %d tiles (i1), 1..%d", a.n, kMaxTiles);
+  OMNI_REQUIRE(a.H >= 1 && a.W >= 1, "region_ocr cut: a frame of %d x %d (i2 x i3)", a.H, a.W);
+  OMNI_REQUIRE(a.R >= 1 && a.R <= kMaxR, "region_ocr cut: R = %d (i4), 1..%d", a.R, kMaxR);
+  OMNI_REQUIRE(a.ldo >= 3 && a.ldo <= 64, "region_ocr cut: pixel pitch %d (i13), 3..64 elements", a.ldo);
+  OMNI_REQUIRE(op->dtype == OMNI_F32 || op->dtype == OMNI_F16, "region_ocr cut: unsupported dtype %d", op->dtype);
+  OMNI_REQUIRE(a.img && a.origins && a.y && a.lut, "region_ocr cut: p0 (frame), p1 (origins), p4 (tiles) or p7 (1/255 table) is NULL");
+  OMNI_REQUIRE((unsigned long long)a.origins % 4 == 0 && (unsigned long long)a.lut % 4 == 0 &&
+               (unsigned long long)a.y % (op->dtype == OMNI_F32 ? 4 : 2) == 0, "region_ocr cut: p1 / p4 / p7 not aligned to their elements");
+  for (int c = 0; c < 3; ++c) OMNI_REQUIRE(a.stdv[c] != 0.0f, "region_ocr cut: std of channel %d (f%d) is 0", c, 3 + c);
+  const dim3 grid((unsigned)(((long long)a.R * a.R + 255) / 256), a.n);
+  if (op->dtype == OMNI_F32) hipLaunchKernelGGL(tile_cut_kernel<float>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(tile_cut_kernel<half_t>, grid, dim3(256), 0, s, a);
+  OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- mode 1
+struct ParseArgs {
+  const int* ids; const unsigned short* table; const float* logp; const int* cells;
+  int* rec; float* sum; int* rows;
+  int n, T, M, table_len, ld_ids, ld_logp, R, eos;
+};
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+
+__device__ __forceinline__ int wave_or(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+  return v;
+}
+
+// one block of one wave per row
+__global__ __launch_bounds__(64) void region_parse_kernel(ParseArgs a) {
+  __shared__ unsigned short cls[kMaxT];        // class of ORIGINAL token j
+  __shared__ unsigned short orig[kMaxT];       // original index of stripped token s
+  __shared__ unsigned short ra[kMaxM], rb[kMaxM], rc[kMaxM];   // region k: original index of its first content token, first and last location token
+  __shared__ int found, kept;
+  const int lane = threadIdx.x, row = blockIdx.x;
+  const int* ids = a.ids + (long long)row * a.ld_ids;
+  int end = a.T;                               // the row is [1, end): in front of the first EOS behind the start token
+  for (int j = 1 + lane; j < a.T; j += 64) {
+    const int id = ids[j];
+    int c = kHard;
+    if (id >= 0 && id < a.table_len) c = min((int)a.table[id], kHard);
+    cls[j] = (unsigned short)c;
+    if (id == a.eos) end = min(end, j);
+  }
+  end = wave_min(end);
+  __syncthreads();
+  int hard = 0;
+  for (int j = 1 + lane; j < end; j += 64) hard |= cls[j] == kHard;
+  hard = wave_or(hard);
+  if (lane == 0) {
+    int s = 0, p = 0, run = 0, k = 0;          // stripped tokens so far, stripped index of the open region's start, location run, regions
+    for (int j = 1; j < end; ++j) {
+      const int c = cls[j];
+      if (c == kStrip) continue;
+      orig[s] = (unsigned short)j;
+      run = c < 1000 ? run + 1 : 0;
+      if (run >= 8 && s - 7 >= p + 1) {        // tokens s - 7 .. s are location tokens and at least one token of content is in front
+        ra[k] = orig[p]; rb[k] = orig[s - 7]; rc[k] = (unsigned short)j;
+        ++k;
+        p = s + 1;
+        run = 0;
+      }
+      ++s;
+    }
+    found = k;
+    kept = 0;
+  }
+  __syncthreads();
+  const int nreg = found;                      // <= (end - 1) / 9 <= M
+  const int* cell = a.cells + (long long)row * 6;
+  for (int k = lane; k < a.M; k += 64) {
+    int* rec = a.rec + ((long long)row * a.M + k) * 16;
+    if (k >= nreg) {
+#pragma unroll
+      for (int t = 0; t < 16; ++t) rec[t] = 0;
+      a.sum[(long long)row * a.M + k] = 0.0f;
+      continue;
+    }
+    const int first = ra[k], b = rb[k], last_loc = rc[k];
+    int cnt = 0, last = first + 1, q = 0;
+    long long lo[2] = {LLONG_MAX, LLONG_MAX}, hi[2] = {LLONG_MIN, LLONG_MIN};   // [0] x, [1] y over the four corners
+    float sum = 0.0f;
+    for (int j = first; j <= last_loc; ++j) {
+      const int c = cls[j];
+      if (c == kStrip) continue;
+      ++cnt;
+      if (a.logp) sum += a.logp[(long long)row * a.ld_logp + j - 1];
+      if (j < b) { last = j + 1; continue; }
+      const long long v = (long long)(((2 * c + 1) * a.R) / 2000) + cell[q & 1];   // exactly 8 tokens get here, all of them bins
+      if (q & 1) { lo[1] = min(lo[1], v); hi[1] = max(hi[1], v); }
+      else { lo[0] = min(lo[0], v); hi[0] = max(hi[0], v); }
+      rec[3 + (q & 7)] = (int)v;
+      ++q;
+    }
+    const long long cx = lo[0] + hi[0], cy = lo[1] + hi[1];                      // the box centre, doubled
+    const bool own = cx >= cell[2] && (cell[3] == INT_MAX || cx < cell[3]) && cy >= cell[4] && (cell[5] == INT_MAX || cy < cell[5]);
+    rec[0] = row; rec[1] = first; rec[2] = last;
+    rec[11] = cnt; rec[12] = own; rec[13] = rec[14] = rec[15] = 0;
+    a.sum[(long long)row * a.M + k] = sum;
+    if (own) atomicAdd(&kept, 1);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    int* r = a.rows + (long long)row * 4;
+    r[0] = nreg; r[1] = kept; r[2] = hard | (end == a.T ? 2 : 0); r[3] = 0;
+  }
+}
+
+int parse_cfg(const omni_op_t* op, ParseArgs& a) {
+  a.n = op->i[1]; a.T = op->i[2]; a.M = op->i[3]; a.table_len = op->i[4];
+  a.ld_ids = op->i[5] ? op->i[5] : a.T; a.ld_logp = op->i[6] ? op->i[6] : a.T - 1; a.R = op->i[7]; a.eos = op->i[8];
+  OMNI_REQUIRE(a.n >= 1 && a.n <= kMaxTiles, "region_ocr parse: %d rows (i1), 1..%d", a.n, kMaxTiles);
+  OMNI_REQUIRE(a.T >= 2 && a.T <= kMaxT, "region_ocr parse: rows of T = %d tokens (i2), 2..%d", a.T, kMaxT);
+  OMNI_REQUIRE(a.M == (a.T - 1) / 9, "region_ocr parse: %d region slots per row (i3), (T - 1) / 9 = %d", a.M, (a.T - 1) / 9);
+  OMNI_REQUIRE(a.table_len >= 1, "region_ocr parse: a class table of %d entries (i4)", a.table_len);
+  OMNI_REQUIRE(a.ld_ids >= a.T && a.ld_logp >= a.T - 1, "region_ocr parse: row strides %d (i5) / %d (i6) below T = %d / T - 1", a.ld_ids, a.ld_logp, a.T);
+  OMNI_REQUIRE(a.R >= 1 && a.R <= kMaxR, "region_ocr parse: R = %d (i7), 1..%d", a.R, kMaxR);
+  return OMNI_OK;
+}
+
+int launch_parse(const omni_op_t* op, hipStream_t s) {
+  ParseArgs a{};
+  if (int rc = parse_cfg(op, a)) return rc;
+  a.ids = (const int*)op->p[0]; a.table = (const unsigned short*)op->p[1]; a.logp = (const float*)op->p[2];
+  a.rec = (int*)op->p[4]; a.sum = (float*)op->p[5]; a.rows = (int*)op->p[6]; a.cells = (const int*)op->p[7];
+  OMNI_REQUIRE(a.ids && a.table && a.rec && a.sum && a.rows && a.cells,
+               "region_ocr parse: p0 (ids), p1 (class table), p4 (records), p5 (sums), p6 (row counters) or p7 (cells) is NULL");
+  OMNI_REQUIRE((unsigned long long)a.ids % 4 == 0 && (unsigned long long)a.table % 2 == 0 && (unsigned long long)a.logp % 4 == 0 &&
+               (unsigned long long)a.rec % 4 == 0 && (unsigned long long)a.sum % 4 == 0 && (unsigned long long)a.rows % 4 == 0 &&
+               (unsigned long long)a.cells % 4 == 0, "region_ocr parse: a pointer is not aligned to its elements");
+  hipLaunchKernelGGL(region_parse_kernel, dim3(a.n), dim3(64), 0, s, a);
+  OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
+}  // namespace
+
+// the bytes mode 1 touches behind p0, p1, p2, p4, p5, p6, p7; false for an op whose slots the launcher refuses (capi.hip::op_extents)
+bool omni_region_ocr_extents(const omni_op_t* op, long long ext[8]) {
+  ParseArgs a{};
+  if (parse_cfg(op, a) != OMNI_OK) return false;
+  ext[0] = ((long long)(a.n - 1) * a.ld_ids + a.T) * 4;
+  ext[1] = (long long)a.table_len * 2;
+  ext[2] = ((long long)(a.n - 1) * a.ld_logp + a.T - 1) * 4;
+  ext[4] = (long long)a.n * a.M * 64; ext[5] = (long long)a.n * a.M * 4; ext[6] = (long long)a.n * 16; ext[7] = (long long)a.n * 24;
+  return true;
+}
+
+int omni_launch_region_ocr(const omni_op_t* op, hipStream_t s) {
+  const int mode = op->i[0];
+  if (mode == 0) return launch_cut(op, s);
+  OMNI_REQUIRE(mode == 1, "region_ocr: mode %d (i0), 0 = tile cut, 1 = region parse", mode);
+  return launch_parse(op, s);
+}

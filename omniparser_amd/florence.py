@@ -669,6 +669,55 @@ def match_topk(queries, gallery, top_k=1, device=None):
         return idx.long(), score
 
 
+# ---- region OCR (OMNI_OP_REGION_OCR, csrc/region_ocr.hip)
+OCR_MAX_T, OCR_MAX_R = 2049, 65536                      # the op's limits (include/omni_amd.h)
+OCR_INF = 2 ** 31 - 1                                   # a cell without an upper end; the lower one is -2^31
+
+
+def ocr_slots(T: int) -> int:
+    """region slots per row of T tokens: a region is at least one token of content and eight location tokens"""
+    return (T - 1) // 9
+
+
+def tile_cut_op(dtype, img_ptr, origins_ptr, y_ptr, lut_ptr, n, H, W, R, ldo):
+    """mode 0: n windows of R x R pixels of the u8 [H, W, 3] frame at the origins i32 [n, 2] -> a caption plan's input rows"""
+    return L.make_op(L.OP_REGION_OCR, dtype, p=[img_ptr, origins_ptr, None, None, y_ptr, None, None, lut_ptr],
+                     i={0: 0, 1: n, 2: H, 3: W, 4: R, 13: ldo},
+                     f={0: CLIP_MEAN[0], 1: CLIP_MEAN[1], 2: CLIP_MEAN[2], 3: CLIP_STD[0], 4: CLIP_STD[1], 5: CLIP_STD[2]})
+
+
+def region_parse_op(ids_ptr, table_ptr, logp_ptr, cells_ptr, rec_ptr, sum_ptr, rows_ptr, n, T, table_len, R, eos, ld_ids=0, ld_logp=0,
+                    slots=None):
+    """mode 1: n rows of T ids (and their log-probabilities, or None) -> records i32 [n x M, 16], sums f32 [n x M], counters i32 [n, 4]"""
+    return L.make_op(L.OP_REGION_OCR, L.F32, p=[ids_ptr, table_ptr, logp_ptr, None, rec_ptr, sum_ptr, rows_ptr, cells_ptr],
+                     i={0: 1, 1: n, 2: T, 3: ocr_slots(T) if slots is None else slots, 4: table_len, 5: ld_ids, 6: ld_logp, 7: R, 8: eos})
+
+
+def ocr_cells(origins, R: int):
+    """The cells table of mode 1 for tiles of R x R pixels at `origins` [(x, y)] (a grid: every x with every y), one row per tile:
+    [origin x, origin y, lo x, hi x, lo y, hi y].  Per axis the boundary between neighbouring tiles is the midpoint of their overlap,
+    held in DOUBLED pixels (origin + next origin + R) so that it is an integer; lo is inclusive, hi exclusive, and the outermost cells
+    have no end (-2^31 / OCR_INF).  A region belongs to the tile whose cell holds the doubled centre of its box on both axes."""
+    def axis(vals):
+        vs = sorted(set(vals))
+        out = {}
+        for k, v in enumerate(vs):
+            out[v] = (-2 ** 31 if k == 0 else vs[k - 1] + v + R, OCR_INF if k == len(vs) - 1 else v + vs[k + 1] + R)
+        return out
+    ax, ay = axis([x for x, _ in origins]), axis([y for _, y in origins])
+    return [[x, y, *ax[x], *ay[y]] for x, y in origins]
+
+
+def check_class_table(class_table) -> torch.Tensor:
+    """`read_regions`' class table as a contiguous int16-viewed u16 host tensor, or a ValueError"""
+    t = class_table
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t.astype(np.int16) if t.dtype == np.uint16 else t)
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() < 1 or t.dtype not in (torch.int16, torch.uint16):
+        raise ValueError("class_table must be a non-empty 1-D u16 table (FlorenceProcessor.loc_class_table())")
+    return t.view(torch.int16).contiguous()
+
+
 _DECODE_TUNING = "unset"
 
 
@@ -1808,7 +1857,7 @@ class Florence2Captioner:
         return self._dec_stream
 
     # ---- decode loop shared by both entry points
-    def _run(self, cp: _CaptionPlans, n: int, max_new: int, defer: bool = False, embeds: Optional[list] = None) -> torch.Tensor:
+    def _run(self, cp: _CaptionPlans, n: int, max_new: int, defer: bool = False, embeds: Optional[list] = None, after=None) -> torch.Tensor:
         run = (lambda p: p.replay(self.stream)) if self.use_graph else (lambda p: p.run(self.stream))
         run(cp.encode_plan)
         if embeds is not None:             # caption_crops(return_embeddings=True): one eager launch behind the encode plan, same stream
@@ -1824,6 +1873,8 @@ class Florence2Captioner:
             if poll and (t + 1) % poll == 0 and t + 1 < max_new and bool(cp.finished[:n].min().item()):
                 break
         self.last_steps = steps
+        if after is not None:              # read_regions: its launches go behind the last step on the same stream; nothing is read back here
+            return after(cp, n)
         if defer:                          # stream-ordered snapshot; the caller reads it back later (no sync here)
             return cp.snapshot(n)
         if cp.beam:                        # finished hypotheses [n, k, T], their scores and generated lengths (synchronises)
@@ -1952,13 +2003,14 @@ class Florence2Captioner:
         return out
 
     def _caption_chunks(self, src, n_all, chunk, R, max_new_tokens, beam, fill, prompt=None, scores=False, controls=None, vocab=None,
-                        embeds=None):
+                        embeds=None, after=None):
         """encode + decode n_all images in chunks of `chunk` on the captioner's stream, each on the plan of its bucket: fill(cp, s, n)
         writes images [s, s + n) into rows [0, n) of that plan's input (`src`: the tensor they come from).  prompt: `prompt_batch`
         of the n_all images (None = the default prompt).  The `_run` result of every chunk, for `_results` (scores: plans that
         also return the token log-probabilities, for `_results_scores`).  controls: non-neutral `GenerationControls` (None = the
         plans without them): every chunk runs on a controls plan, its block uploaded on the stream before the first step.  vocab: a
-        checked `CaptionVocabulary` (None = none): every chunk runs on a vocabulary plan, the trie block uploaded the same way."""
+        checked `CaptionVocabulary` (None = none): every chunk runs on a vocabulary plan, the trie block uploaded the same way.
+        after: after(cp, n) is called behind every chunk's last step, on the stream, INSTEAD of the read-back; its results are the parts."""
         n_txt = prompt[2] if prompt else None
         block = controls.pack(self.w.vocab, self.w.forced_bos) if controls else None
         trie = vocab.pack() if vocab else None
@@ -1979,7 +2031,8 @@ class Florence2Captioner:
                 fill(cp, s, n)
                 if prompt:
                     cp.set_prompt(prompt[0][s:s + n].to(self.device, non_blocking=True), prompt[1][s:s + n].to(self.device, non_blocking=True), n)
-                parts.append(self._run(cp, n, max_new_tokens, **({"embeds": embeds} if embeds is not None else {})))
+                parts.append(self._run(cp, n, max_new_tokens, **({"embeds": embeds} if embeds is not None else {}),
+                                       **({"after": after} if after is not None else {})))
         return parts
 
     def _embed_chunks(self, src, n_all, chunk, R, fill) -> torch.Tensor:
@@ -2119,6 +2172,83 @@ class Florence2Captioner:
         else:
             out = (self._results(parts, beam)[0],)
         return out[0] if len(out + emb) == 1 else tuple(out) + emb
+
+    # ---- region OCR over native-resolution tiles (OMNI_OP_REGION_OCR)
+    def launch_tiles(self, cp, n, image_u8, origins, stream):
+        """one OMNI_OP_REGION_OCR mode-0 launch on `stream`: the n windows of cp.R x cp.R pixels at `origins` (int32 [n, 2] x y on the
+        device) of one HWC uint8 frame, normalised into rows [0, n) of cp.x_in; pixels outside the frame are white"""
+        lut, _ = self._crop_tables(64)
+        H, W = image_u8.shape[:2]
+        L.launch(tile_cut_op(self.dtype, image_u8.data_ptr(), origins.data_ptr(), cp.x_in.ptr, lut.data_ptr(), n, H, W, cp.R, cp.x_in.ld), stream)
+
+    @torch.inference_mode()
+    def read_regions(self, image_u8: torch.Tensor, max_new_tokens=1024, overlap=128, prompt_ids=None, class_table=None, controls=None):
+        """Read the text of a screenshot with its places: Florence-2's <OCR_WITH_REGION> task over tiles of the captioner's own
+        resolution R, cut from the HWC uint8 frame on the device WITHOUT resizing (a whole frame squeezed to R x R is unreadable).
+        Tiles: `ScreenParser.tile_origins(W, H, R, R, overlap)`, row-major; they are the rows of the chunked greedy decode
+        `describe_image` runs (scores plans, `long_plan_rows` per chunk, the early-exit poll), filled by OMNI_OP_REGION_OCR mode 0;
+        mode 1 parses every chunk's ids and log-probabilities on the device behind its last step.  One read-back at the end.
+        prompt_ids: the task's prompt (bos ... eos), `FlorenceProcessor.prompt_ids("<OCR_WITH_REGION>")`; class_table: the u16
+        per-token class table, `FlorenceProcessor.loc_class_table()`; controls: as in `caption_crops`.
+        Returns an object with `origins` [(x, y)] per tile, `records` i32 [tiles, M, 16], `sums` f32 [tiles, M], `rows` i32 [tiles, 4]
+        `ids` i64 [tiles, T] and `logp` f32 [tiles, T - 1] aligned with ids[:, 1:] (for rows re-parsed on the host)
+        (T = max_new_tokens + 1, M = (T - 1) // 9) — the op's outputs as include/omni_amd.h describes them:
+        a region's content as a column range of `ids`, its quad in frame pixels, its token count and log-probability sum, and whether
+        its own tile keeps it (`ocr_cells`); per tile the regions found and kept and the flags (1: a token the device does not parse
+        — re-parse the row from text; 2: cut off at max_new_tokens).
+        ValueError before anything reaches the device: no prompt or class table, overlap outside 0 <= overlap < R, max_new_tokens
+        outside `check_max_new`, a frame that is not HWC uint8, bad controls."""
+        R = int(self.resolution)
+        if prompt_ids is None or class_table is None:
+            raise ValueError("read_regions needs prompt_ids (the <OCR_WITH_REGION> prompt) and class_table (FlorenceProcessor.loc_class_table())")
+        table = check_class_table(class_table)
+        if isinstance(overlap, bool) or not isinstance(overlap, int) or not 0 <= overlap < R:
+            raise ValueError(f"overlap must be an integer in 0..{R - 1} (tiles are {R} x {R}), got {overlap!r}")
+        self.check_max_new(max_new_tokens)
+        controls = self.generation_controls(controls, max_new_tokens, None)
+        if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8 or image_u8.dim() != 3 or image_u8.shape[2] != 3 \
+                or image_u8.shape[0] < 1 or image_u8.shape[1] < 1:
+            raise ValueError("image_u8 must be a uint8 tensor [H, W, 3]")
+        from .pipeline import ScreenParser
+        H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
+        origins = ScreenParser.tile_origins(W, H, R, R, overlap)[0]
+        n_all, T = len(origins), max_new_tokens + 1
+        M = ocr_slots(T)
+        prompt = self.prompt_batch([list(prompt_ids)] * n_all, R)
+        dev = self.device
+        image_u8 = image_u8.to(dev).contiguous()
+        with self._lock:
+            if image_u8.is_cuda:               # a screenshot the caller is still producing on its own stream
+                self.stream.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(self.stream):
+                org =torch.tensor(origins, dtype=torch.int32).to(dev, non_blocking=True)
+                cells = torch.tensor(ocr_cells(origins, R), dtype=torch.int32).to(dev, non_blocking=True)
+                tab = table.to(dev, non_blocking=True)
+                rec = torch.zeros((n_all, max(M, 1), 16), dtype=torch.int32, device=dev)
+                sums = torch.zeros((n_all, max(M, 1)), dtype=torch.float32, device=dev)
+                rows = torch.zeros((n_all, 4), dtype=torch.int32, device=dev)
+                ids = torch.full((n_all, T), int(self.w.pad), dtype=torch.int32, device=dev)     # columns no step reached: pad
+                logp = torch.zeros((n_all, T), dtype=torch.float32, device=dev)
+            at = [0]
+
+            def fill(cp, s, n):
+                at[0] = s
+                self.launch_tiles(cp, n, image_u8, org[s:s + n], self.stream)
+
+            def after(cp, n):
+                s = at[0]
+                L.launch(region_parse_op(cp.ids.data_ptr(), tab.data_ptr(), cp.logp.data_ptr() + 4, cells[s:s + n].data_ptr(),
+                                         rec[s:s + n].data_ptr(), sums[s:s + n].data_ptr(), rows[s:s + n].data_ptr(), n, T, tab.numel(), R,
+                                         int(self.w.eos), ld_ids=T, ld_logp=T), self.stream)
+                done = self.last_steps + 1             # the early exit leaves the columns behind it as `reset` left them
+                ids[s:s + n, :done].copy_(cp.ids[:n, :done], non_blocking=True)
+                logp[s:s + n, :done].copy_(cp.logp[:n, :done], non_blocking=True)
+
+            self._caption_chunks(image_u8, n_all, 128, R, max_new_tokens, None, fill, prompt, True, controls, after=after)
+            with torch.cuda.stream(self.stream):
+                out = SimpleNamespace(origins=origins, records=rec[:, :M].cpu(), sums=sums[:, :M].cpu(), rows=rows.cpu(), ids=ids.cpu().long(),
+                                      logp=logp[:, 1:].cpu())
+        return out
 
     # ---- teacher-forced scoring of given texts (OMNI_OP_GREEDY_STEP p5)
     def _check_labels(self, labels, n):

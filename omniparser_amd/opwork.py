@@ -9,7 +9,7 @@ Slot meanings: include/omni_amd.h."""
 NAMES = {1: "conv_igemm/conv_split", 2: "avgpool2", 3: "maxpool", 4: "resize_nearest", 5: "letterbox", 6: "detect_decode", 7: "nms",
          8: "dwconv3", 9: "layernorm", 10: "attn_rows (window / MHA)", 11: "chan_attn", 12: "proj_prep", 13: "assemble", 14: "embed_step",
          15: "attn_decode", 16: "greedy_step", 17: "crop_resize", 18: "dwconv3_ln", 19: "split_convert", 20: "hand_off", 21: "overlay",
-         22: "png_pack", 23: "png_deflate", 24: "mlp_fused", 26: "greedy_ctrl_step", 28: "visual_match"}
+         22: "png_pack", 23: "png_deflate", 24: "mlp_fused", 26: "greedy_ctrl_step", 28: "visual_match", 29: "region_ocr"}
 
 MFMA_KINDS = (1, 24, 10)          # priced against the dense f16 MFMA peak; everything else against HBM
 
@@ -65,6 +65,12 @@ def op_work(op, esz=4):
         if i[0] == 1:                               # queries and gallery once (a perfectly cached execution), the partials out
             return 2 * m * n * D, 4 * (m + n) * D + 8 * m * splits * kk
         return 0, 8 * m * splits * kk + 8 * m * kk
+    if k == 29:                                     # i0: 0 = tile cut (u8 window in, normalised pixels out), 1 = region parse
+        if i[0] == 0:
+            n, R, ldo = i[1], i[4], i[13]
+            return 2 * 3 * n * R * R, n * R * R * (3 + ldo * esz)
+        n, T, M = i[1], i[2], i[3]                  # ids and log-probabilities in, records, sums and row counters out (class table: cached)
+        return 0, n * (4 * T + (4 * (T - 1) if op.p[2] else 0) + 68 * M + 16 + 24)
     return 0, 0
 
 
@@ -87,6 +93,8 @@ def op_shape(op):
         return (i[10], i[9], i[7] if i[7] > 0 else i[8])
     if k == 28:                                     # embed: (crops, D, 0); match: (queries, D, gallery rows)
         return (i[1], i[3], 0 if i[0] == 0 else i[2])
+    if k == 29:                                     # cut: (tiles, R, 0); parse: (rows, T, 0)
+        return (i[1], i[4] if i[0] == 0 else i[2], 0)
     return (i[0], i[3], 0)
 
 
@@ -102,4 +110,6 @@ def op_kernel(op):
         return "chan_attn (fold)" if op.i[9] == 1 else "chan_attn (scores + fold)"
     if op.kind == 28:
         return ("visual_match (embed)", "visual_match (partial top-k)", "visual_match (merge)")[op.i[0]] if 0 <= op.i[0] <= 2 else "visual_match"
+    if op.kind == 29:
+        return ("region_ocr (tile cut)", "region_ocr (parse)")[op.i[0]] if 0 <= op.i[0] <= 1 else "region_ocr"
     return NAMES.get(op.kind, str(op.kind))

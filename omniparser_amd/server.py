@@ -168,6 +168,9 @@ def main():
     ap.add_argument("--caption_vocabulary", type=json.loads, default=None,
                     help="closed set of icon captions as a JSON list of strings (they need the tokenizer.json next to the checkpoint) or of "
                          "token id lists, e.g. '[\"close\", \"settings\", \"search\"]': every captioned icon gets exactly one of them")
+    ap.add_argument("--ocr_provider", choices=["florence"], default=None,
+                    help="\"florence\": read the text of every screenshot with the caption model itself (<OCR_WITH_REGION> over tiles; it needs "
+                         "the tokenizer.json next to the checkpoint); default: no OCR of its own, the request's \"ocr\" field if any")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
     a = ap.parse_args()

@@ -3,9 +3,9 @@
 Mirrors the public contract of ref:util/omniparser.py:7-32 — the same config keys (`som_model_path`,
 `caption_model_name`, `caption_model_path`, `BOX_TRESHOLD`), `parse(image_base64) -> (labeled_png_b64,
 parsed_content_list)` — on top of the gfx950 detector / captioner adapters.  OCR is not part of the hot
-path (SURVEY §8): an optional `ocr_provider` callable in the config supplies `(texts, xyxy_px_boxes)`;
-without it the screenshot is parsed with icons only, exactly what the reference produces when its OCR
-engine returns nothing.
+path: an optional `ocr_provider` in the config supplies `(texts, xyxy_px_boxes)` — a callable,
+or "florence" for the caption model's own `<OCR_WITH_REGION>` reading (utils.FlorenceOCR); without it the
+screenshot is parsed with icons only, exactly what the reference produces when its OCR engine returns nothing.
 """
 import base64
 import io
@@ -43,6 +43,32 @@ class Omniparser(object):
         self.caption_model_processor = U.get_caption_model_processor(
             model_name=config["caption_model_name"], model_name_or_path=config["caption_model_path"], device=device)
         self.ocr_provider: Optional[Callable] = config.get("ocr_provider")
+        # ocr_provider: None (no OCR of its own), a callable image -> (texts, xyxy px boxes), or "florence": the caption model reads
+        # the screenshot itself (utils.FlorenceOCR over this object's caption model: <OCR_WITH_REGION> over tiles of the captioner's
+        # resolution; it needs the tokenizer.json next to the checkpoint).  ocr_max_new_tokens (tokens per tile, default 1024),
+        # ocr_overlap (pixels shared by neighbouring tiles, default 128), ocr_min_confidence (0..1, default 0) and ocr_generation
+        # (generation controls of the reading, as caption_generation) belong to it; ranges the captioner knows are checked per call.
+        ocr_keys = {k: config[k] for k in ("ocr_max_new_tokens", "ocr_overlap", "ocr_min_confidence", "ocr_generation") if config.get(k) is not None}
+        if isinstance(self.ocr_provider, str):
+            if self.ocr_provider != "florence":
+                raise ValueError(f"ocr_provider must be None, a callable or \"florence\", got {self.ocr_provider!r}")
+            for k, lo in (("ocr_max_new_tokens", 1), ("ocr_overlap", 0)):
+                v = ocr_keys.get(k)
+                if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < lo):
+                    raise ValueError(f"{k} must be an integer >= {lo}, got {v!r}")
+            mc = ocr_keys.get("ocr_min_confidence")
+            if mc is not None and (isinstance(mc, bool) or not isinstance(mc, (int, float)) or not 0.0 <= mc <= 1.0):
+                raise ValueError(f"ocr_min_confidence must be a number in 0..1, got {mc!r}")
+            if "ocr_generation" in ocr_keys:
+                from ..florence import GenerationControls
+                if not isinstance(ocr_keys["ocr_generation"], dict):
+                    raise ValueError(f"ocr_generation must be a dict of generation controls or None, got {ocr_keys['ocr_generation']!r}")
+                GenerationControls.of(ocr_keys["ocr_generation"])
+            self.ocr_provider = U.FlorenceOCR(self.caption_model_processor, **{k[4:]: v for k, v in ocr_keys.items()})
+        elif ocr_keys:
+            raise ValueError(f"{sorted(ocr_keys)} belong to ocr_provider=\"florence\"")
+        elif self.ocr_provider is not None and not callable(self.ocr_provider):
+            raise ValueError(f"ocr_provider must be None, a callable or \"florence\", got {self.ocr_provider!r}")
         # crop resolution of the captioner: 768 = the reference's CPU branch (bicubic to 768x768; the parity target and the
         # default here), 64 = its cuda branch (do_resize=False, ref:util/utils.py:120-121).  An explicit choice, not a device side effect.
         if config.get("caption_resolution") is not None:

@@ -143,6 +143,41 @@ class FlorenceProcessor:
             raise ValueError(f"the prompt {text!r} needs a tokenizer: {where} is missing (only the default <CAPTION> prompt works without it)")
         return [self.bos_id] + list(self.tok.encode(text, add_special_tokens=False).ids) + [self.eos_id]
 
+    def loc_class_table(self):
+        """(class table u16 [vocab] as numpy, per-token texts) for OMNI_OP_REGION_OCR and `parse_ocr_regions`, built once from the
+        tokenizer.json: a token's class is its location bin 0..999 (`<loc_N>`), L.OCR_CLASS_STRIP (`<s>`, `</s>`, `<pad>`, which
+        transformers deletes from the text before it matches), L.OCR_CLASS_TEXT, or L.OCR_CLASS_HARD when its text is empty or holds
+        a newline or '<' — the cases in which matching tokens and matching the decoded text can differ.  A token's text is what
+        transformers' `Florence2PostProcessor.decode_with_spans` gives it: the token itself when it is special, else the decoder's
+        rendering of that ONE token (not of the sequence).  ValueError: no tokenizer.json (naming the file), or a tokenizer whose
+        `<loc_0>` .. `<loc_999>` are not 1000 ascending contiguous ids."""
+        if getattr(self, "_loc", None) is not None:
+            return self._loc
+        if self.tok is None:
+            where = Path(self.model_dir) / "tokenizer.json" if self.model_dir is not None else "tokenizer.json (no model directory was given)"
+            raise ValueError(f"reading text regions needs a tokenizer with <loc_0>..<loc_999>: {where} is missing")
+        base = self.tok.token_to_id("<loc_0>")
+        if base is None or any(self.tok.token_to_id(f"<loc_{k}>") != base + k for k in range(1000)):
+            raise ValueError(f"{Path(self.model_dir) / 'tokenizer.json'}: <loc_0>..<loc_999> must be 1000 contiguous ascending token ids "
+                             "(the tokenizer of a Florence-2 checkpoint)")
+        n, dec = self.vocab_size, self.tok.decoder
+        table = np.full((n,), L.OCR_CLASS_HARD, dtype=np.uint16)
+        texts = [""] * n
+        for t in range(n):
+            tok = self.tok.id_to_token(t)
+            if tok is None:
+                continue
+            if tok in ("<s>", "</s>", "<pad>"):
+                table[t], texts[t] = L.OCR_CLASS_STRIP, tok
+                continue
+            texts[t] = tok if (t in self.special or dec is None) else dec.decode([tok])
+            if base <= t < base + 1000:
+                table[t] = t - base
+            elif texts[t] and "\n" not in texts[t] and "<" not in texts[t]:
+                table[t] = L.OCR_CLASS_TEXT
+        self._loc = (table, texts)
+        return self._loc
+
     def batch_decode(self, ids, skip_special_tokens=True):
         special = self.special
         out = []
@@ -534,6 +569,139 @@ def describe_image(image_source, caption_model_processor, task="<MORE_DETAILED_C
     texts = [t.strip() for t in processor.batch_decode(ids, skip_special_tokens=True)]
     out = [(t, r) for t, r in zip(texts, ids)] if return_ids else texts
     return out if many else out[0]
+
+
+# ------------------------------------------------------------------------------------------ OCR by the caption model
+_OCR_PATTERN = r"(.+?)" + r"<loc_(\d+)>" * 8            # transformers' Florence2PostProcessor pattern of the "ocr" task
+
+
+def dequantize_bin(b: int, size: int) -> int:
+    """pixel of location bin b (0..999) on an axis of `size` pixels: the bin's centre, truncated —
+    Florence2PostProcessor.dequantize(...).int() in integers, and what OMNI_OP_REGION_OCR computes"""
+    return ((2 * b + 1) * size) // 2000
+
+
+def parse_ocr_regions(ids_row, processor, size):
+    """The <OCR_WITH_REGION> answer of ONE image parsed on the host FROM ITS TEXT, as transformers'
+    Florence2PostProcessor.parse_ocr_from_text_and_spans parses it: the tokens are rendered one by one (`loc_class_table` texts), the
+    strings `<s>`, `</s>`, `<pad>` are deleted, and `(.+?)(<loc_N>){8}` is matched on what is left.  The device parses tokens
+    instead (OMNI_OP_REGION_OCR) and flags the rows in which that can differ; this is what those rows fall back to.
+    ids_row: the decoder start token and the generated ids (a row of `Florence2Captioner.read_regions().ids`); only the columns in
+    front of the first EOS behind column 0 count.  size: (width, height) the bins are de-quantised to.
+    -> [{"text" (stripped), "quad" [x0, y0, .. x3, y3] in pixels of the image, "columns": the columns of `ids_row` whose text the
+    match covers}]"""
+    _table, texts = processor.loc_class_table()
+    row = [int(t) for t in (ids_row.tolist() if hasattr(ids_row, "tolist") else ids_row)]
+    end = next((j for j in range(1, len(row)) if row[j] == processor.eos_id), len(row))
+    text, owner = "", []
+    for j in range(1, end):
+        t = texts[row[j]] if 0 <= row[j] < len(texts) else ""
+        text += t
+        owner += [j] * len(t)
+    for needle in ("<s>", "</s>", "<pad>"):                 # str.replace, with the owners of the deleted characters deleted too
+        at = text.find(needle)
+        while at >= 0:
+            text = text[:at] + text[at + len(needle):]
+            del owner[at:at + len(needle)]
+            at = text.find(needle, at)
+    import re
+    w, h = size
+    out = []
+    for m in re.finditer(_OCR_PATTERN, text):
+        bins = [int(g) for g in m.groups()[1:]]
+        out.append({"text": m.group(1).strip(), "quad": [dequantize_bin(b, h if k & 1 else w) for k, b in enumerate(bins)],
+                    "columns": sorted(set(owner[m.start():m.end()]))})
+    return out
+
+
+def _owns(cell, quad):
+    """`florence.ocr_cells`' rule on the host: the doubled centre of the quad's box lies in the cell on both axes"""
+    from ..florence import OCR_INF
+    cx, cy = min(quad[0::2]) + max(quad[0::2]), min(quad[1::2]) + max(quad[1::2])
+    return cell[2] <= cx and (cell[3] == OCR_INF or cx < cell[3]) and cell[4] <= cy and (cell[5] == OCR_INF or cy < cell[5])
+
+
+@torch.inference_mode()
+def read_text_regions(image_source, caption_model_processor, max_new_tokens=1024, overlap=128, min_confidence=0.0, generation=None,
+                      return_stats=False):
+    """Built-in OCR: the text of a screenshot with its places, read by the caption model itself (Florence-2's <OCR_WITH_REGION>
+    task) — `Florence2Captioner.read_regions`: the frame is cut into tiles of the captioner's resolution on the device, unscaled,
+    `overlap` pixels shared between neighbours; every tile is decoded greedily and its answer parsed on the device.
+    image_source: a path, a PIL image, an HWC uint8 array or a device tensor.  generation: generation controls as in
+    `describe_image`.  -> [{"text", "quad" [[x, y] x 4] and "bbox" [x0, y0, x1, y1] in frame pixels, "confidence", "tile"}], tile
+    by tile, in reading order of the answer within a tile.  A region seen by two overlapping tiles is returned by the one whose cell
+    holds the centre of its box (`florence.ocr_cells`); regions whose stripped text is empty and regions below `min_confidence` are
+    dropped.  confidence = exp(mean log-probability of the region's tokens, content and location tokens alike).  A line of text
+    that crosses a cell boundary is read twice, once per tile, each time as far as that tile sees it; both readings survive only
+    when their box centres fall into their own cells.  Rows the device flags as holding a token it does not parse (a newline, a
+    '<') are re-parsed from their text by `parse_ocr_regions` under the same ownership rule.
+    return_stats=True: (regions, per tile {"found", "kept", "truncated", "fallback"}).
+    ValueError before anything reaches the device: no tokenizer.json next to the checkpoint (naming the file), a tokenizer without
+    Florence-2's location tokens, overlap outside 0 <= overlap < resolution, max_new_tokens beyond the decoder, min_confidence
+    outside 0..1."""
+    import math
+    from ..florence import ocr_cells
+    model, processor = caption_model_processor["model"], caption_model_processor["processor"]
+    if isinstance(min_confidence, bool) or not isinstance(min_confidence, (int, float)) or not 0.0 <= min_confidence <= 1.0:
+        raise ValueError(f"min_confidence must be a number in 0..1, got {min_confidence!r}")
+    table, texts = processor.loc_class_table()
+    prompt = processor.prompt_ids("<OCR_WITH_REGION>")
+    if isinstance(image_source, str):
+        image_source = Image.open(image_source)
+    if isinstance(image_source, Image.Image):
+        image_source = np.asarray(image_source.convert("RGB"))
+    out = model.read_regions(_frame_on(image_source, model.device), max_new_tokens=max_new_tokens, overlap=overlap, prompt_ids=prompt,
+                             class_table=table, controls=generation)
+    R = int(model.resolution)
+    cells = ocr_cells(out.origins, R)
+    regions, stats = [], []
+    for r, (ox, oy) in enumerate(out.origins):
+        found, kept, flags = (int(v) for v in out.rows[r, :3])
+        ids = out.ids[r].tolist()
+        if flags & 1:                                       # from the text, on the host
+            cands = []
+            for reg in parse_ocr_regions(ids, processor, (R, R)):
+                quad = [v + (oy if k & 1 else ox) for k, v in enumerate(reg["quad"])]
+                cols = reg["columns"]
+                cands.append((reg["text"], quad, float(sum(float(out.logp[r, j - 1]) for j in cols)), len(cols), _owns(cells[r], quad)))
+            found, kept = len(cands), sum(1 for c in cands if c[4])
+        else:
+            cands = []
+            for k in range(found):
+                rec = out.records[r, k].tolist()
+                text = "".join(texts[t] for t in ids[rec[1]:rec[2]] if table[t] != L.OCR_CLASS_STRIP).strip()
+                cands.append((text, rec[3:11], float(out.sums[r, k]), rec[11], bool(rec[12])))
+        stats.append({"found": found, "kept": kept, "truncated": bool(flags & 2), "fallback": bool(flags & 1)})
+        for text, quad, total, count, own in cands:
+            conf = math.exp(total / count) if count else 0.0
+            if own and text and conf >= min_confidence:
+                regions.append({"text": text, "quad": [[quad[0], quad[1]], [quad[2], quad[3]], [quad[4], quad[5]], [quad[6], quad[7]]],
+                                "bbox": [min(quad[0::2]), min(quad[1::2]), max(quad[0::2]), max(quad[1::2])], "confidence": conf, "tile": r})
+    return (regions, stats) if return_stats else regions
+
+
+class FlorenceOCR:
+    """The caption model as an OCR engine.  `readtext(image_np, **easyocr_args) -> [(quad, text, confidence)]` is EasyOCR's reader
+    contract, so `set_ocr_engine(easyocr_reader=FlorenceOCR(cmp))` makes `check_ocr_box` read with it (EasyOCR's own keywords —
+    text_threshold, paragraph, ... — are accepted and ignored); calling the object with a PIL image returns (texts, xyxy boxes), the
+    `ocr_provider` contract of `Omniparser`.  defaults: max_new_tokens, overlap, min_confidence, generation of `read_text_regions`."""
+
+    def __init__(self, caption_model_processor, **defaults):
+        bad = sorted(set(defaults) - {"max_new_tokens", "overlap", "min_confidence", "generation"})
+        if bad:
+            raise ValueError(f"FlorenceOCR: unknown settings {bad} (max_new_tokens, overlap, min_confidence, generation)")
+        self.caption_model_processor = caption_model_processor
+        self.defaults = defaults
+
+    def read(self, image):
+        return read_text_regions(image, self.caption_model_processor, **self.defaults)
+
+    def readtext(self, image_np, **easyocr_args):
+        return [(r["quad"], r["text"], r["confidence"]) for r in self.read(image_np)]
+
+    def __call__(self, pil_image):
+        regions = self.read(pil_image)
+        return [r["text"] for r in regions], [r["bbox"] for r in regions]
 
 
 @torch.inference_mode()
