@@ -91,7 +91,13 @@ enum {
    *           multiply weight matrix b: p1 + b * i27 bytes (i27 % 16 == 0, i27 >= Cout * K * 4, or 0 = every image reads p1), each a
    *           format-B matrix of its own with its own power of two: p6 = f32[M / n] of 2^-k, read in place of f1 (NULL = f1 for all).
    *           n must be a multiple of the row tile the launcher takes (256, or 128 for short token matrices / OMNI_GEMM_TILE=128x128),
-   *           else OMNI_E_ARG: the image of a tile is then uniform.  Written by OMNI_OP_CHAN_ATTN's fold mode (i8 = 1)
+   *           else OMNI_E_ARG: the image of a tile is then uniform (n % 256 != 0 takes the 128-row tile).  Written by OMNI_OP_CHAN_ATTN's
+   *           fold mode (i8 = 1).  i27 = 0 with p6 set = one shared weight and a 2^-k per image: the fold GEMM W''_b = W'_b . Wv of a channel
+   *           block with Wv folded in (x = the packed per-image matrices, B * C rows of C, n = C; w = Wv^T packed on the host; p6[b] = the
+   *           product of the image's 2^-k and the weight's 2^-kv, written by OMNI_OP_CHAN_ATTN i11 = 1; y = f32 [B][C][C])
+   *  i29 = 1 (i20 = 2 with i26 > 0 only, additive; 0 = p2 is one bias vector): PER-IMAGE BIAS.  p2 = f32[M / i26][Cout], 16-byte aligned;
+   *           the rows of image b add p2 + b * Cout.  Without per-image mode, with the scores epilogue, with p2 NULL or misaligned:
+   *           OMNI_E_ARG.  The same vector in every row of the table gives the bits of the shared-bias launch
    *  i28 = 1 (i20 = 2 only, additive; 0 = the epilogues above): SCORES EPILOGUE for the q|k launch of a folded channel block.  The weight
    *           rows (and the bias) are ordered [q_0 | k_0 | q_1 | k_1 | ...], 32 rows per part, so that columns [64 g, 64 g + 64) of the
    *           product are q and k of channel group g.  Nothing is written to p4 (it may be NULL and is not touched); every 256-row tile
@@ -187,7 +193,13 @@ enum {
    *  follows run as always
    *  i10 = t > 0 (additive; f32 plans, t % 8 == 0, i5 % t == 0; 0 = i5): TOKENS PER PARTIAL.  Every chunk of i5 tokens is kept as i5 / t
    *  partials of t tokens: chunks = ceil(N / t) in the layout of p5, in the scores launch and in the softmax's sum — the op at i5 = t, bit
-   *  for bit.  The captioner's folded stages run i5 = 1024, i10 = 256 (the row tile of OMNI_OP_CONV i28 = 1) */
+   *  for bit.  The captioner's folded stages run i5 = 1024, i10 = 256 (the row tile of OMNI_OP_CONV i28 = 1)
+   *  i11 = 1 (fold mode only, additive; C % 128 == 0): Wv FOLDED IN AS WELL — the projection will read the block's LayerNorm output h,
+   *  y = h . (W'_b Wv)^T + b''_b.  p1 = f32[C * C + 2 C]: Wp, then the v bias bv, then the projection bias bp.  p2 = f32[B * C * C + B * C]:
+   *  W' as always, and behind the B matrices the bias table b''_b[o] = (sum_c W'_b[o][c] bv[c]) + bp[o], one fma chain per output over c
+   *  ascending from 0, computed from the f32 W'_b.  f1 = 2^-kv of the packed Wv^T (0 => 1): p6[b] = 2^-k * f1 (exact), the scale of the fold
+   *  GEMM (OMNI_OP_CONV i26 = C, i27 = 0) that overwrites p2's matrices with W''_b = W'_b . Wv; OMNI_OP_SPLIT_CONVERT i6 = 1 then re-packs
+   *  them into p3 / p6, and the projection runs with OMNI_OP_CONV i29 = 1 on the table.  Everything else as i11 = 0, bit for bit */
   OMNI_OP_CHAN_ATTN = 11,
   /* projector input (florence2 :568-590): y[b] = [mean_n(x+pos+t) ; x+pos+t]; p0 x [B,N,C] p1 pos2d f32[N,C] p2 temporal f32[C] p4 y [B,N+1,C]
    *  i0 B i1 N i3 C */
@@ -252,7 +264,12 @@ enum {
    *  i0 B i1 H i2 W i3 C (<= 1024) i6 = 1: h in format B (f32 plans); f0 eps */
   OMNI_OP_DWCONV3_LN = 18,
   /* f32 channel slice of a token matrix -> format B (OMNI_OP_CONV i20 = 2), in place when p0 == p4 and the slices coincide.
-   *  p0 x [rows, ldi] p4 y [rows, ldo]; i0*i1 rows i3 C i4 ldi i5 in_coff i13 ldo i14 out_coff (all multiples of 16) */
+   *  p0 x [rows, ldi] p4 y [rows, ldo]; i0*i1 rows i3 C i4 ldi i5 in_coff i13 ldo i14 out_coff (all multiples of 16)
+   *  i6 = 1 (additive; f32 plans): PER-MATRIX POWER OF TWO.  p0 = i0 square f32 matrices [C][C] (i1 = i3 = i4 = i13 = C, C % 64 == 0,
+   *  i5 = i14 = 0), each packed as format B of x * 2^k with k per matrix such that the largest |x 2^k| lies in [2^12, 2^13) (clamped to
+   *  +-24; 0 for a zero matrix; hi and lo rounded to nearest) — the packing OMNI_OP_CHAN_ATTN's fold mode gives W'_b, here for the W''_b
+   *  of a block with Wv folded in.  p6 = f32[i0] receives 2^-k, p5 = f32[i0 * (C / 64) * (C / 32)] scratch (block maxima: no atomics,
+   *  nothing to zero between replays) */
   OMNI_OP_SPLIT_CONVERT = 19,
   /* Detect -> caption hand-off of ONE screenshot on the device: ref:util/utils.py:432-453 (ratio boxes, int_box_area filter),
    * remove_overlap_new (:241-319, incl. its list.remove quirk), the "content is None last" ordering (:449-451) and the crop

@@ -118,6 +118,7 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
         const long long nimg = (M + i[26] - 1) / i[26];
         ext[1] += (nimg - 1) * (long long)i[27];
         ext[6] = nimg * 4;
+        if (i[29] == 1) ext[2] = nimg * Cout * 4;            // per-image bias table
       }
       if (i[20] == 2 && i[28] == 1) {                        // scores epilogue: p7 = one 4 KB partial per 256-row chunk and 64-column group, no y
         ext[7] = (M / 256) * (Cout / 64) * 4096;
@@ -130,6 +131,7 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
       const long long B = i[0], N = i[1], C = i[3], G = i[4], ct = i[10] > 0 ? i[10] : (i[5] > 0 ? i[5] : 1);   // i10: tokens per partial
       ext[0] = B * N * 3 * C * esz; ext[4] = B * N * C * esz; ext[5] = B * G * ((N + ct - 1) / ct) * 1024 * 4;
       if (i[8] == 1) { ext[1] = C * C * 4; ext[2] = ext[3] = B * C * C * 4; ext[6] = B * 4; ext[7] = B * (C / 64) * G * 4; }
+      if (i[8] == 1 && i[11] == 1) { ext[1] += 2 * C * 4; ext[2] += B * C * 4; }   // p1 = Wp | bv | bp, the bias table behind W'
       break;
     }
     case OMNI_OP_BEAM_STEP: {
@@ -200,6 +202,7 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
     case OMNI_OP_SPLIT_CONVERT: {
       const long long rows = (long long)i[0] * i[1];
       ext[0] = span(rows, i[4], i[5], i[3]); ext[4] = span(rows, i[13], i[14], i[3]);
+      if (i[6] == 1) { ext[5] = (long long)i[0] * (i[3] / 64) * (i[3] / 32) * 4; ext[6] = (long long)i[0] * 4; }   // re-pack: block maxima, 2^-k
       break;
     }
     case OMNI_OP_AVGPOOL2: case OMNI_OP_MAXPOOL: case OMNI_OP_RESIZE_NEAREST: {

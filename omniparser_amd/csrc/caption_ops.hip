@@ -1690,7 +1690,56 @@ __global__ __launch_bounds__(256, 2) void chan_apply_mfma_split_kernel(ChanArgs 
 struct FoldArgs {
   const float* ws; const float* wp; float* wf; float* bmax; unsigned char* wb; float* osc;
   int C, G, chunks, nblk;
+  float oscmul;                       // power of two multiplied into the 2^-k of the scale table (1 unless i11 = 1: the 2^-kv of the packed Wv^T)
+  const float* bv; const float* bp; float* bias;   // i11 = 1: v bias, projection bias, the per-image bias table [B][C]
 };
+
+// ---- Wv folded in as well (OMNI_OP_CHAN_ATTN i11): y = h . W''_b^T + b''_b with W''_b = W'_b . Wv and b''_b[o] = sum_c W'_b[o][c] bv[c] + bp[o].
+// The product W'_b . Wv is a gemm_dma launch of the planner's (packed W'_b rows as the "token" operand, Wv^T as the weight, per-image 2^-k
+// times the weight's 2^-kv from the scale table); around it:
+//   chan_fold_bias_kernel  (i11 = 1, behind chan_fold_kernel) b''_b from the f32 W'_b: one fma chain per output over c ascending from 0,
+//                          then + bp[o].  64 outputs per block, W' staged through LDS in 64 x 128 tiles (coalesced rows; C % 128 == 0)
+//   chan_fold_max_kernel   (OMNI_OP_SPLIT_CONVERT i6 = 1, the re-pack) max |W''| of 2048 consecutive elements per block into the slots chan_fold_pack_kernel reduces
+//                          (nblk * 2048 = C * C), then chan_fold_pack_kernel (below) on the W'' the GEMM wrote over W'
+__global__ __launch_bounds__(256) void chan_fold_bias_kernel(FoldArgs a) {
+  constexpr int TC = 128, PITCH = TC + 1;                      // 64 rows x 128 columns per step; odd pitch: conflict-free row reads
+  __shared__ float sW[64 * PITCH];
+  __shared__ float sB[TC];
+  const int ob = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const float* W = a.wf + ((long long)b * a.C + ob * 64) * a.C;
+  float acc = 0.0f;
+  for (int c0 = 0; c0 < a.C; c0 += TC) {
+    __syncthreads();                                           // the previous tile has been read
+    for (int e = tid; e < 64 * (TC / 4); e += 256) {           // all four waves load: 16 bytes per lane, rows coalesced
+      const int r = e / (TC / 4), q = e % (TC / 4);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(W + (long long)r * a.C + c0 + 4 * q);
+      float* d = sW + r * PITCH + 4 * q;
+      d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    }
+    if (tid < TC) sB[tid] = a.bv[c0 + tid];
+    __syncthreads();
+    if (tid < 64) {                                            // one chain per output, c ascending
+#pragma unroll 8
+      for (int i = 0; i < TC; ++i) acc = fmaf(sW[tid * PITCH + i], sB[i], acc);
+    }
+  }
+  if (tid < 64) a.bias[(long long)b * a.C + ob * 64 + tid] = acc + a.bp[ob * 64 + tid];
+}
+
+__global__ __launch_bounds__(256) void chan_fold_max_kernel(FoldArgs a) {
+  __shared__ float smax[4];
+  const int e = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const float* src = a.wf + (long long)b * a.C * a.C + (long long)e * 2048 + tid * 8;
+  const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
+  float m = 0.0f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) m = fmaxf(m, fmaxf(fabsf(v0[q]), fabsf(v1[q])));
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((tid & 63) == 0) smax[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) a.bmax[(long long)b * a.nblk + e] = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
+}
 
 __global__ __launch_bounds__(256) void chan_fold_kernel(FoldArgs a) {
   __shared__ float sA[32][32];
@@ -1742,7 +1791,7 @@ __global__ __launch_bounds__(256) void chan_fold_pack_kernel(FoldArgs a) {
     k = max(-24, min(24, k));
   }
   const float up = __builtin_bit_cast(float, (unsigned)(127 + k) << 23);
-  if (blockIdx.x == 0 && tid == 0) a.osc[b] = __builtin_bit_cast(float, (unsigned)(127 - k) << 23);
+  if (blockIdx.x == 0 && tid == 0) a.osc[b] = __builtin_bit_cast(float, (unsigned)(127 - k) << 23) * a.oscmul;   // exact: powers of two
   const int gpr = a.C / 16;
   const int idx = blockIdx.x * 256 + tid;
   if (idx >= a.C * gpr) return;
@@ -2948,6 +2997,22 @@ static int launch_attn_rows(const omni_op_t* op, hipStream_t s) {
   return OMNI_OK;
 }
 
+// OMNI_OP_SPLIT_CONVERT i6 = 1: the re-pack of a channel block with Wv folded in — B square f32 matrices (W''_b, written by the fold GEMM)
+// to format B with a power of two of their own each, as chan_fold_pack_kernel packs W'_b
+int omni_launch_chan_repack(const omni_op_t* op, hipStream_t s) {
+  FoldArgs f{};
+  const int B = op->i[0], C = op->i[3];
+  f.wf = (float*)op->p[0]; f.wb = (unsigned char*)op->p[4]; f.bmax = (float*)op->p[5]; f.osc = (float*)op->p[6];
+  OMNI_REQUIRE(op->dtype == OMNI_F32 && f.wf && f.wb && f.bmax && f.osc, "split_convert (i6 = 1): f32 plans, p0 / p4 / p5 / p6");
+  OMNI_REQUIRE(B > 0 && C > 0 && C % 64 == 0 && op->i[1] == C && op->i[4] == C && op->i[5] == 0 && op->i[13] == C && op->i[14] == 0,
+               "split_convert (i6 = 1): i0 square matrices of i1 = i3 = i4 = i13 = C, C %% 64 == 0, no channel offsets (C %d)", C);
+  f.C = C; f.G = C / 32; f.nblk = (C / 64) * (C / 32); f.oscmul = 1.0f;
+  hipLaunchKernelGGL(chan_fold_max_kernel, dim3(f.nblk, B), dim3(256), 0, s, f);
+  hipLaunchKernelGGL(chan_fold_pack_kernel, dim3((C * (C / 16) + 255) / 256, B), dim3(256), 0, s, f);
+  OMNI_HIP_CHECK(hipGetLastError());
+  return OMNI_OK;
+}
+
 static int launch_chan_attn(const omni_op_t* op, hipStream_t s) {
   ChanArgs a{};
   a.qkv = op->p[0]; a.o = op->p[4]; a.ws = (float*)op->p[5];
@@ -2958,6 +3023,10 @@ static int launch_chan_attn(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE(!fold || (op->dtype == OMNI_F32 && a.chunk_tokens % 8 == 0 && a.C % 64 == 0 && op->p[1] && op->p[2] && op->p[3] && op->p[6] && op->p[7]),
                "chan_attn: fold mode needs an f32 plan, C %% 64 == 0, chunk_tokens %% 8 == 0 and p1 / p2 / p3 / p6 / p7");
   OMNI_REQUIRE(!a.osplit || op->dtype == OMNI_F32, "chan_attn: split output needs an f32 plan");
+  // i11 = 1: Wv folded in as well (see chan_fold_bias_kernel): fold mode + the per-image bias table behind W' in p2 (p1 = Wp | bv | bp) and
+  // f1 = the 2^-kv multiplied into the scale table
+  const int vfold = op->i[11];
+  OMNI_REQUIRE(vfold == 0 || (vfold == 1 && fold && a.C % 128 == 0), "chan_attn: i11 = %d needs fold mode (i8 = 1) and C %% 128 == 0, and is 0 or 1", vfold);
   // i9 = 1: the workspace already holds the score partials (written by the scores epilogue of the q|k GEMM, OMNI_OP_CONV i28): no scores launch
   const bool have_scores = op->i[9] == 1;
   // i10 > 0: tokens per score partial where the partials are finer than the chunk i5 (the row tile of the q|k GEMM's scores epilogue):
@@ -2981,7 +3050,12 @@ static int launch_chan_attn(const omni_op_t* op, hipStream_t s) {
       f.ws = a.ws; f.wp = (const float*)op->p[1]; f.wf = (float*)op->p[2]; f.wb = (unsigned char*)op->p[3]; f.osc = (float*)op->p[6];
       f.bmax = (float*)op->p[7];
       f.C = a.C; f.G = a.G; f.chunks = a.chunks; f.nblk = (a.C / 64) * a.G;
+      f.oscmul = (vfold == 1 && op->f[1] != 0.0f) ? op->f[1] : 1.0f;
       hipLaunchKernelGGL(chan_fold_kernel, dim3(a.C / 64, a.G, a.B), dim3(256), 0, s, f);
+      if (vfold == 1) {
+        f.bv = f.wp + (long long)a.C * a.C; f.bp = f.bv + a.C; f.bias = f.wf + (long long)a.B * a.C * a.C;
+        hipLaunchKernelGGL(chan_fold_bias_kernel, dim3(a.C / 64, a.B), dim3(256), 0, s, f);
+      }
       hipLaunchKernelGGL(chan_fold_pack_kernel, dim3((a.C * (a.C / 16) + 255) / 256, a.B), dim3(256), 0, s, f);
       OMNI_HIP_CHECK(hipGetLastError());
       return OMNI_OK;

@@ -42,6 +42,8 @@ struct GemmArgs {
   // image mt / img_tiles, whose weight matrix lies img * w_img_stride bytes behind w and whose 2^-k is img_oscale[img].
   // img_tiles == 0: one weight matrix and `oscale` for all rows
   int img_tiles; unsigned w_img_stride; const float* img_oscale;
+  // per-image bias (OMNI_OP_CONV i29 = 1; per-image mode only): image img adds bias[img * bias_img_stride + n]; 0 = one bias vector
+  int bias_img_stride;
   // scores epilogue (GEMM_EPI_SCORES below): no output matrix — `y` is the channel-attention workspace f32 [image][group][chunk][32][32]
   // and img_tiles the chunks per image (the struct, part of MlpArgs too, keeps its layout)
 };
@@ -81,7 +83,8 @@ struct RowBuf {
 // that end with the wave's last channel of row min(M, m0 + BM) - 1.  2^-k is a power of two, so acc * 2^-k is exact and ONE fma
 // gives the bits of multiply + add (outside the subnormal range).
 template <int BM, int BN, int WM, int WN, int TM, int TN, int LDS_BYTES, int ACT, bool OSPLIT, bool RES>
-__device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& a, unsigned char* lds, int m0, int n0, int wave, int lane, float osc) {
+__device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& a, const float* bias, unsigned char* lds, int m0, int n0, int wave,
+                                              int lane, float osc) {
   constexpr int NW = WM * WN;
   const int wm = wave / WN, wn = wave % WN;
   const int hsel = lane >> 5;
@@ -107,7 +110,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        bq[j][q] = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + nw0 + 4 * hsel + j * 32 + q * 8) : f32x4{0.f, 0.f, 0.f, 0.f};
+        bq[j][q] = bias ? *reinterpret_cast<const f32x4*>(bias + nw0 + 4 * hsel + j * 32 + q * 8) : f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 rres[8];
     auto load_res = [&](int i) {                             // residual rows of token tile i in the read-phase layout (rows >= M read as 0)
 #pragma unroll
@@ -499,7 +502,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_dma_kernel(GemmArgs a) {
   if constexpr (ACT == GEMM_EPI_SCORES)
     gemm_scores_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE>(acc, a, lds, img, __builtin_amdgcn_readfirstlane(mt) - img * a.img_tiles, n0, wave, lane, osc);
   else
-    gemm_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE, ACT, OSPLIT, RES>(acc, a, lds, m0, n0, wave, lane, osc);
+    gemm_epilogue<BM, BN, WM, WN, TM, TN, NSTAGE * STAGE, ACT, OSPLIT, RES>(acc, a, a.bias + (long long)img * a.bias_img_stride, lds, m0, n0, wave,
+                                                                            lane, osc);   // (stride 0 unless i29: NULL stays NULL)
 #endif
 }
 
@@ -684,7 +688,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_kernel(MlpArgs a) {
   }
   omni_report_range(amax);
   // ---- epilogue: 2^-k2, fc2 bias, residual, coalesced f32 rows (gemm_epilogue: four waves x 32 tokens x 128 channels)
-  gemm_epilogue<NW * 32, C, NW, 1, 1, OB, 2 * STAGE, OMNI_ACT_NONE, false, true>(acc2, a.ep, lds, m0, 0, wave, lane, a.ep.oscale);
+  gemm_epilogue<NW * 32, C, NW, 1, 1, OB, 2 * STAGE, OMNI_ACT_NONE, false, true>(acc2, a.ep, a.ep.bias, lds, m0, 0, wave, lane, a.ep.oscale);
 #endif
 }
 
@@ -775,6 +779,13 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
     a.w_img_stride = (unsigned)op->i[27];
     a.img_oscale = (const float*)op->p[6];
   }
+  // per-image bias (i29 = 1): p2 = f32[M / i26][N], image b adds row b — the b''_b of a channel block with Wv folded in (caption_ops.hip)
+  OMNI_REQUIRE(op->i[29] == 0 || op->i[29] == 1, "gemm_dma: unknown bias mode %d (i29)", op->i[29]);
+  if (op->i[29] == 1) {
+    OMNI_REQUIRE(rows_per_img > 0 && op->i[28] == 0, "gemm_dma: a per-image bias (i29) needs per-image mode (i26 > 0) and no scores epilogue");
+    OMNI_REQUIRE(a.bias && (uintptr_t)a.bias % 16 == 0, "gemm_dma: the per-image bias table (p2) must be a 16-byte aligned pointer");
+    a.bias_img_stride = a.N;
+  }
   if (scores) {
     OMNI_REQUIRE(a.y, "gemm_dma: the scores epilogue needs its workspace (p7)");
     OMNI_REQUIRE(rows_per_img > 0 && rows_per_img % 256 == 0, "gemm_dma: the scores epilogue needs whole 256-row chunks per image (i26 = %d)", rows_per_img);
@@ -790,6 +801,8 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
     const long long mt256 = (a.M + 255) / 256;
     if (mt256 * (a.N / (tile == 0 ? 256 : 128)) < 256) tile = (tile == 0 && mt256 * (a.N / 128) >= 256) ? 1 : 2;
   }
+  // per-image weights over images shorter than a 256-row tile (the fold GEMM of a C = 128 channel block: 128 rows per image)
+  if (rows_per_img > 0 && rows_per_img % 256 != 0) tile = 2;
   if (const char* e = getenv("OMNI_GEMM_TILE")) {
     if (!strcmp(e, "256x128")) tile = 1;
     else if (!strcmp(e, "128x128")) tile = 2;
@@ -807,6 +820,8 @@ int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s) {
 
 // OMNI_OP_SPLIT_CONVERT: f32 channel slice -> format B (in place allowed).
 int omni_launch_split_convert(const omni_op_t* op, hipStream_t s) {
+  OMNI_REQUIRE(op->i[6] == 0 || op->i[6] == 1, "split_convert: unknown mode %d (i6)", op->i[6]);
+  if (op->i[6] == 1) return omni_launch_chan_repack(op, s);   // per-matrix power of two (caption_ops.hip)
   const long long rows = (long long)op->i[0] * (op->i[1] > 0 ? op->i[1] : 1);
   const int C = op->i[3], ldi = op->i[4], in_coff = op->i[5], ldo = op->i[13], out_coff = op->i[14];
   OMNI_REQUIRE(op->dtype == OMNI_F32 && op->p[0] && op->p[4], "split_convert: f32 plans, non-null pointers");

@@ -209,6 +209,7 @@ __device__ __forceinline__ f32x2 omni_gelu2(f32x2 v) {
 int omni_launch_conv(const omni_op_t* op, hipStream_t s);
 int omni_launch_gemm_dma(const omni_op_t* op, hipStream_t s);
 int omni_launch_split_convert(const omni_op_t* op, hipStream_t s);
+int omni_launch_chan_repack(const omni_op_t* op, hipStream_t s);   // OMNI_OP_SPLIT_CONVERT i6 = 1
 int omni_launch_mlp_fused(const omni_op_t* op, hipStream_t s);
 int omni_launch_avgpool2(const omni_op_t* op, hipStream_t s);
 int omni_launch_maxpool(const omni_op_t* op, hipStream_t s);

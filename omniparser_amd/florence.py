@@ -1243,9 +1243,14 @@ class _CaptionPlans(_StepPlans):
             chunks = (N + (partial_tokens or chunk_tokens) - 1) // (partial_tokens or chunk_tokens)
             cws = pb.raw((B * w.groups[s] * chunks * 1024,), torch.float32, zero=False)
             scores_in_gemm = fold and bool(cap.chan_scores_in_gemm)
-            fold_wf = fold_wb = fold_sc = fold_mx = None
+            # Wv folded in as well (cap.fold_chan_v): y = h . (W'_b Wv)^T + b''_b — the v launch and the v tensor go, the fold pays
+            # C^3 MACs per image and block where the v launch pays N C^2.  Rule: every folded stage (N >= 4 C; measured per stage)
+            fold_v = fold and bool(cap.fold_chan_v) and N >= 4 * C
+            fold_wf = fold_wb = fold_sc = fold_mx = fold_bias = None
             if fold:                                      # stage scratch, image-major: an exact-row twin uses the first n images' part
-                fold_wf = pb.raw((B * C * C,), torch.float32, zero=False)
+                # fold_v: the per-image bias table b''_b [B][C] lies behind the B matrices (OMNI_OP_CHAN_ATTN i11 = 1)
+                fold_wf = pb.raw((B * C * C + (B * C if fold_v else 0),), torch.float32, zero=False)
+                fold_bias = fold_wf[B * C * C:] if fold_v else None
                 fold_wb = pb.raw((B * C * C,), torch.float32, zero=False)
                 fold_sc = pb.raw((B,), torch.float32, zero=False)
                 fold_mx = pb.raw((B * (C // 64) * w.groups[s],), torch.float32, zero=False)
@@ -1285,17 +1290,32 @@ class _CaptionPlans(_StepPlans):
                             pb.conv_scores(tokens(hbuf), wqs, bqs, cws, N)
                         else:
                             pb.conv(tokens(hbuf), wqk, bqk, tokens(qkv.slice(0, 2 * C)), 1)
-                        vs = tokens(qkv.slice(2 * C, C))
-                        pb.conv(tokens(hbuf), wv, bv, vs, 1, out_split=True)
                         pkey = pre + "channel_attn.proj"
-                        wplain, bproj = W.f32(pkey + ".weight"), W.f32(pkey + ".bias")
-                        pb.keep += [wplain, bproj]
-                        pb.add_op(L.make_op(L.OP_CHAN_ATTN, dt,
-                                            p=[qkv.ptr, wplain.data_ptr(), fold_wf.data_ptr(), fold_wb.data_ptr(), None, cws.data_ptr(),
-                                               fold_sc.data_ptr(), fold_mx.data_ptr()],
-                                            i={0: B, 1: N, 3: C, 4: w.groups[s], 5: chunk_tokens, 6: 1 if (attn_split and grp["dma"]) else 0, 8: 1,
-                                               9: 1 if scores_in_gemm else 0, 10: partial_tokens}))
-                        pb.conv_per_image(vs, fold_wb, fold_sc, bproj, tokens(B_), tokens(B_), N)
+                        chan_p = [qkv.ptr, None, fold_wf.data_ptr(), fold_wb.data_ptr(), None, cws.data_ptr(), fold_sc.data_ptr(), fold_mx.data_ptr()]
+                        chan_i = {0: B, 1: N, 3: C, 4: w.groups[s], 5: chunk_tokens, 6: 1 if (attn_split and grp["dma"]) else 0, 8: 1,
+                                  9: 1 if scores_in_gemm else 0, 10: partial_tokens}
+                        if fold_v:
+                            # no v launch: softmax + fold + pack leave W'_b (and b''_b, and 2^-k 2^-kv as the scale), the fold GEMM turns it
+                            # into W''_b = W'_b Wv over fold_wf, the re-pack (OMNI_OP_SPLIT_CONVERT i6 = 1) packs that, and the projection reads h itself
+                            wvt, wpb = W.cached((key, dt, "dma-vT|wp|bv|bp"), lambda: (
+                                pb.pack_weight_dma(sd[key + ".weight"][2 * C:].float().t().contiguous()),
+                                pb.upload(torch.cat([sd[pkey + ".weight"].float().reshape(-1), sd[key + ".bias"][2 * C:].float(),
+                                                     sd[pkey + ".bias"].float()]))))
+                            pb.keep += [wvt, wpb]
+                            chan_p[1] = wpb.data_ptr()
+                            pb.add_op(L.make_op(L.OP_CHAN_ATTN, dt, p=chan_p, i={**chan_i, 11: 1}, f={1: wvt.omni_oscale}))
+                            pb.fold_gemm(fold_wb, fold_sc, wvt, fold_wf, B, C)
+                            pb.repack_per_image(fold_wf, fold_wb, fold_sc, fold_mx, B, C)
+                            pb.conv_per_image(tokens(hbuf), fold_wb, fold_sc, fold_bias, tokens(B_), tokens(B_), N, bias_per_image=True)
+                            pb.flops += 2 * B * N * C * C      # the v layer's algorithmic work: unchanged by no launch running it
+                        else:
+                            vs = tokens(qkv.slice(2 * C, C))
+                            pb.conv(tokens(hbuf), wv, bv, vs, 1, out_split=True)
+                            wplain, bproj = W.f32(pkey + ".weight"), W.f32(pkey + ".bias")
+                            pb.keep += [wplain, bproj]
+                            chan_p[1] = wplain.data_ptr()
+                            pb.add_op(L.make_op(L.OP_CHAN_ATTN, dt, p=chan_p, i=chan_i))
+                            pb.conv_per_image(vs, fold_wb, fold_sc, bproj, tokens(B_), tokens(B_), N)
                     else:
                         linear(pre + "channel_attn.qkv", hbuf, qkv)
                         pb.add_op(L.make_op(L.OP_CHAN_ATTN, dt, p=[qkv.ptr, None, None, None, att.ptr, cws.data_ptr()],
@@ -1484,6 +1504,8 @@ class Florence2Captioner:
     attn_split_out = True     # attention kernels write format B for the projection GEMM themselves
     fold_chan_proj = True     # channel attention's apply pass folded into a per-image projection weight where N >= 4 C (f32 LDS-DMA plans;
                               # DaViT stages 0-2 at 768x768, nothing at 64x64): OMNI_OP_CHAN_ATTN i8 = 1 + OMNI_OP_CONV i26 / i27 / p6
+    fold_chan_v = True        # folded stages: Wv folded into the per-image projection weight as well — no v launch, the projection reads the
+                              # block's LayerNorm output with a per-image bias (OMNI_OP_CHAN_ATTN i11, OMNI_OP_CONV i29)
     chan_scores_in_gemm = True   # folded stages: the q|k launch reduces its tiles to the score partials in its epilogue (OMNI_OP_CONV i28 / p7)
                               # and OMNI_OP_CHAN_ATTN starts at the softmax (i9 = 1); off: plain q|k launch + the standalone scores kernel
                               # over the same 256-token chunks — bit-identical results (the A/B and test switch)

@@ -26,10 +26,16 @@ def op_work(op, esz=4):
         if i[20] == 2 and i[28] == 1:               # scores epilogue: no y, one 4 KB partial per 256-row chunk and 64-column group
             return 2 * M * N * K + 2 * M * N * 16, esz * (M * K + N * K + (M // 256) * (N // 64) * 1024)
         nw = M // i[26] if (i[20] == 2 and i[26] > 0) else 1          # per-image weights: one matrix per image
+        if i[20] == 2 and i[26] > 0 and i[27] == 0:  # the fold GEMM W''_b = W'_b . Wv: not work of the network (its 2 M N K MACs run, but the
+            return 0, esz * (M * K + N * K + M * N)  # count keeps the v layer instead, below), operands read and written once
+        if i[20] == 2 and i[29] == 1:                # projection with Wv folded in: carries the v layer's algorithmic work too (K = N = C)
+            return 4 * M * N * K, esz * (i[0] * i[1] * i[2] * i[3] + nw * N * K + nw * N + M * N * (2 if op.p[3] else 1))
         return 2 * M * N * K, esz * (i[0] * i[1] * i[2] * i[3] + nw * N * K + M * N * (2 if op.p[3] else 1))
     if k == 24:                                     # fc1 + GELU + fc2 + residual: h in, residual in, y out, both weight matrices
         rows, C, hid = i[0] * max(i[1], 1), i[3], i[12]
         return 4 * rows * C * hid, esz * (3 * rows * C + 2 * C * hid)
+    if k == 19 and i[6] == 1:                       # re-pack of W'' = W' . Wv: f32 matrices in, format B out
+        return 0, esz * 2 * i[0] * i[3] * i[3]
     if k in (2, 3, 4):
         return 0, esz * (i[0] * i[1] * i[2] * i[3] + i[0] * max(i[10], 1) * max(i[11], 1) * i[3])
     if k in (8, 18):
@@ -103,9 +109,13 @@ def op_kernel(op):
     if op.kind == 1:
         if op.i[20] == 2 and op.i[28] == 1:
             return "gemm_dma (scores epilogue)"
+        if op.i[20] == 2 and op.i[26] > 0 and op.i[27] == 0:
+            return "gemm_dma (fold W' . Wv)"
         if op.i[20] == 2 and op.i[26] > 0:
-            return "gemm_dma (per-image weights)"
+            return "gemm_dma (per-image weights + bias)" if op.i[29] == 1 else "gemm_dma (per-image weights)"
         return "gemm_dma" if op.i[20] == 2 else ("conv_split" if op.i[20] else "conv_igemm")
+    if op.kind == 19 and op.i[6] == 1:
+        return "split_convert (re-pack W'')"
     if op.kind == 11 and op.i[8] == 1:
         return "chan_attn (fold)" if op.i[9] == 1 else "chan_attn (scores + fold)"
     if op.kind == 28:

@@ -337,17 +337,21 @@ class PlanBuilder:
         return t
 
     def conv_per_image(self, x: View, w_img: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor], out: View,
-                       res: Optional[View], rows_per_img: int):
+                       res: Optional[View], rows_per_img: int, bias_per_image: bool = False):
         """pointwise layer on the LDS-DMA GEMM whose weight matrix differs per image (OMNI_OP_CONV i20 = 2 with i26 / i27 / p6):
         image b = rows [b * rows_per_img, (b + 1) * rows_per_img) of x multiplies the format-B matrix b of `w_img` ([images, Cout * Cin]
-        4-byte elements, written on the device by OMNI_OP_CHAN_ATTN's fold mode) and scales[b] = its 2^-k."""
+        4-byte elements, written on the device by OMNI_OP_CHAN_ATTN's fold mode) and scales[b] = its 2^-k.
+        bias_per_image: `bias` is a table f32 [images, Cout] and image b adds its row b (OMNI_OP_CONV i29 = 1)."""
         cout, K = out.C, x.C
         M = x.B * x.H * x.W
         assert self.dtype == L.F32 and x.fmt == "split" and x.ld % 16 == 0 and x.coff % 16 == 0 and cout % 128 == 0 and K % 32 == 0
         assert (out.B, out.H, out.W) == (x.B, x.H, x.W) and M % rows_per_img == 0
         nimg = M // rows_per_img
         assert w_img.numel() * w_img.element_size() >= nimg * cout * K * 4 and scales.dtype == torch.float32 and scales.numel() >= nimg
-        assert bias is None or (bias.dtype == torch.float32 and bias.numel() == cout and bias.device.type == self.device.type)
+        if bias_per_image:
+            assert bias is not None and bias.dtype == torch.float32 and bias.numel() >= nimg * cout and bias.device.type == self.device.type
+        else:
+            assert bias is None or (bias.dtype == torch.float32 and bias.numel() == cout and bias.device.type == self.device.type)
         if res is not None:
             assert (res.B, res.H, res.W, res.C) == (out.B, out.H, out.W, out.C) and res.fmt == "f32"
         self.ops.append(L.make_op(
@@ -356,12 +360,38 @@ class PlanBuilder:
                None, scales.data_ptr()],
             i={0: x.B, 1: x.H, 2: x.W, 3: K, 4: x.ld, 5: x.coff, 6: 1, 7: 1, 8: 1, 9: 0, 10: x.H, 11: x.W, 12: cout, 13: out.ld, 14: out.coff,
                15: L.ACT_NONE, 16: res.ld if res is not None else 0, 17: res.coff if res is not None else 0, 20: 2,
-               26: rows_per_img, 27: cout * K * 4}))
+               26: rows_per_img, 27: cout * K * 4, **({29: 1} if bias_per_image else {})}))
         self.keep += [w_img, scales] + ([bias] if bias is not None else [])
         out.fmt = "f32"
         self.flops += 2 * M * cout * K                     # the projection's algorithmic work: unchanged by where its weights come from
         self.bytes += 4 * (M * K + nimg * cout * K + M * cout * (2 if res is not None else 1))
         return out
+
+    def fold_gemm(self, w_img: torch.Tensor, scales: torch.Tensor, wvt: torch.Tensor, out: torch.Tensor, nimg: int, C: int):
+        """W''_b = W'_b . Wv of a channel block with Wv folded in (OMNI_OP_CONV i20 = 2, i26 = C, i27 = 0, p6 = scales): the packed per-image
+        matrices `w_img` [nimg * C rows of C] are the "token" operand (weight and activation format B are the same bytes), `wvt` = Wv^T
+        packed once on the host is the shared weight, `out` takes f32 [nimg][C][C].  scales[b] holds the PRODUCT of the image's 2^-k and
+        wvt's 2^-kv (written by OMNI_OP_CHAN_ATTN i11 = 1).  Not algorithmic work of the network: nothing is added to flops / bytes (the v
+        layer it replaces stays in the count, see florence.py)."""
+        assert self.dtype == L.F32 and C % 128 == 0 and getattr(wvt, "omni_fmt", 0) == 2 and wvt.numel() == 2 * C * C
+        assert w_img.numel() * w_img.element_size() >= nimg * C * C * 4 and out.numel() >= nimg * C * C and out.dtype == torch.float32
+        assert scales.dtype == torch.float32 and scales.numel() >= nimg
+        self.ops.append(L.make_op(
+            L.OP_CONV, self.dtype,
+            p=[w_img.data_ptr(), wvt.data_ptr(), None, None, out.data_ptr(), None, scales.data_ptr()],
+            i={0: nimg, 1: C, 2: 1, 3: C, 4: C, 5: 0, 6: 1, 7: 1, 8: 1, 9: 0, 10: C, 11: 1, 12: C, 13: C, 14: 0, 15: L.ACT_NONE, 20: 2,
+               26: C, 27: 0}))
+        self.keep += [w_img, scales, wvt, out]
+
+    def repack_per_image(self, wf: torch.Tensor, w_img: torch.Tensor, scales: torch.Tensor, maxima: torch.Tensor, nimg: int, C: int):
+        """the re-pack behind `fold_gemm` (OMNI_OP_SPLIT_CONVERT i6 = 1): f32 matrices wf [nimg][C][C] -> format B in `w_img` with a power of
+        two per image, chosen as `split_f16_b` chooses it, 2^-k into `scales`; `maxima` = f32 [nimg * (C / 64) * (C / 32)] scratch."""
+        assert self.dtype == L.F32 and C % 64 == 0 and wf.numel() >= nimg * C * C and w_img.numel() * w_img.element_size() >= nimg * C * C * 4
+        assert scales.numel() >= nimg and maxima.numel() >= nimg * (C // 64) * (C // 32)
+        self.ops.append(L.make_op(L.OP_SPLIT_CONVERT, self.dtype,
+                                  p=[wf.data_ptr(), None, None, None, w_img.data_ptr(), maxima.data_ptr(), scales.data_ptr()],
+                                  i={0: nimg, 1: C, 3: C, 4: C, 5: 0, 6: 1, 13: C, 14: 0}))
+        self.keep += [wf, w_img, scales, maxima]
 
     @staticmethod
     def qk_group_rows(C: int):
