@@ -452,9 +452,29 @@ enum {
    *    p5 sums f32[i1 x M]: logp over exactly those n tokens, added in ascending column order (0 with p2 = NULL and in unused slots)
    *    p6 rows i32[i1, 4] {regions found, regions kept, flags, 0}; flags bit 0 = the row holds a HARD token (the host re-parses
    *    it from text), bit 1 = no EOS in the generated part (cut off at max_new_tokens).
-   * OMNI_E_ARG (nothing launched, nothing written): any value outside its range, M != (T - 1) / 9, a NULL pointer other than p2, a
-   * misaligned pointer.  The pointer check covers exactly these extents.  The op's dtype matters to mode 0 only.  Plan bundles and
-   * the model-level entry points do not use it. */
+   *  i0 = 3, box parse (region_boxes_kernel, one 64-lane block per row): the answers of the tasks that reply "phrase <loc>x4 ..."
+   *    (<OD>, <DENSE_REGION_CAPTION>, <OPEN_VOCABULARY_DETECTION>, <CAPTION_TO_PHRASE_GROUNDING>: grammar 0) or boxes alone
+   *    (<REGION_PROPOSAL>: grammar 1).  Slots, the row, the classes, the cells and the flags as in mode 1, except:
+   *    i3 = M, box slots per row: exactly (T - 1) / 4   i9 = grammar, 0 = phrases with boxes, 1 = boxes only
+   *    The row's non-STRIP tokens are cut into alternating maximal runs: a text run [t, a) (classes >= 1000; empty only at the
+   *    row's start), then a run of r location bins [a, a + r).  carry = none.
+   *    grammar 1: a run with r >= 4 gives r / 4 boxes, four bins each from a, and an empty phrase.
+   *    grammar 0: start = carry if there is one, else t if the text run is not empty, else none.  start and r >= 4: a phrase with
+   *    content [start, a), lead = (start is the carry), r / 4 boxes from a; carry = none.  No start and r >= 5: a phrase that is the
+   *    single token a, lead = 1, (r - 1) / 4 boxes from a + 1; carry = none.  Otherwise carry = the run's last token.  lead: the
+   *    phrase's first token is a location token whose text counts WITHOUT its first character (transformers' pattern
+   *    [^<]+(<loc_n>){4,} starts behind the '<' of a location token no earlier match consumed).  r mod 4 left-over bins are ignored.
+   *    p4 records i32[i1 x M, 16], box k of row r at slot r M + k: {r, c0, c1, x0, y0, x1, y1, cloc, n_content, kept, phrase, lead,
+   *    0, 0, 0, 0}: c0 / c1 the ORIGINAL columns of the phrase's first and one-past-last non-STRIP token (c0 = c1 = cloc in grammar
+   *    1), corners ((2 bin + 1) R) / 2000 + origin, cloc the original column of the box's first location token, n_content the
+   *    phrase's non-STRIP tokens, phrase its ordinal in the row (the boxes of one phrase share it), kept = (x0 + x1, y0 + y1) lies in
+   *    the row's cell on both axes.  Unused slots are zero.
+   *    p5 sums f32[i1 x M, 2] {logp over the phrase's n_content tokens, logp over the box's four location tokens}, each added in
+   *    ascending column order (0 with p2 = NULL and in unused slots)
+   *    p6 rows i32[i1, 4] {boxes found, boxes kept, flags, phrases found}
+   * OMNI_E_ARG (nothing launched, nothing written): any value outside its range, M != (T - 1) / 9 (mode 3: (T - 1) / 4), a grammar
+   * outside 0..1, any other i0, a NULL pointer other than p2, a misaligned pointer.  The pointer check covers exactly these extents.
+   * The op's dtype matters to mode 0 only.  Plan bundles and the model-level entry points do not use it. */
   OMNI_OP_REGION_OCR = OMNI_OP_VISUAL_MATCH + 1,   /* 29 (spelled like the three kinds above) */
   OMNI_OP__END
 };

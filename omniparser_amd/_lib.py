@@ -24,6 +24,7 @@ OP_GREEDY_CTRL_STEP = 26
 OP_GREEDY_VOCAB_STEP = 27
 OP_VISUAL_MATCH = 28
 OP_REGION_OCR = 29
+OCR_MODE_CUT, OCR_MODE_PARSE, OCR_MODE_BOXES = 0, 1, 3              # OMNI_OP_REGION_OCR's i0 (2 is refused)
 OCR_CLASS_STRIP, OCR_CLASS_TEXT, OCR_CLASS_HARD = 1000, 1001, 1002      # include/omni_amd.h::OMNI_OCR_CLASS_*
 CAND_BYTES = 32
 ABI_VERSION = 3         # include/omni_amd.h::OMNI_ABI_VERSION — a library built from other headers is refused at load time

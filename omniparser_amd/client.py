@@ -72,6 +72,18 @@ class OmniParserClient:
             raise RuntimeError(f"{self.url} -> HTTP {resp.status_code}: {getattr(resp, 'text', '')[:200]}")
         return self._finish(resp.json(), b64, self._size(image, b64))
 
+    def locate(self, image: ImageLike, phrases: Optional[Sequence[str]], task: Optional[str] = None) -> list:
+        """POST /locate/: the boxes of `phrases` in the image, [{"label", "query", "bbox" [x0, y0, x1, y1] px, "confidence", ...}]"""
+        payload = {"base64_image": encode_image(image), "phrases": list(phrases) if phrases is not None else None}
+        if task is not None:
+            payload["task"] = task
+        url = self.url.rstrip("/")
+        url = (url[: -len("/parse")] if url.endswith("/parse") else url) + "/locate/"
+        resp = self._post(url, json=payload)
+        if getattr(resp, "status_code", 200) != 200:
+            raise RuntimeError(f"{url} -> HTTP {resp.status_code}: {getattr(resp, 'text', '')[:200]}")
+        return resp.json()["boxes"]
+
     def parse_batch(self, images: Sequence[ImageLike], ocr: Optional[Sequence[Optional[dict]]] = None) -> list:
         b64 = [encode_image(im) for im in images]
         items = [{"base64_image": b} if not (ocr and ocr[i]) else {"base64_image": b, "ocr": ocr[i]} for i, b in enumerate(b64)]

@@ -1,5 +1,5 @@
-// OMNI_OP_REGION_OCR: Florence-2's <OCR_WITH_REGION> task over native-resolution tiles of a screenshot.  Two modes (i0), see
-// include/omni_amd.h:
+// OMNI_OP_REGION_OCR: Florence-2's <OCR_WITH_REGION> task and its box-answer tasks over native-resolution tiles of a screenshot.
+// Three modes (i0), see include/omni_amd.h:
 //
 //   0 tile cut      n windows of R x R pixels of the HBM-resident u8 [H, W, 3] frame, at origins read from a device table, rescaled
 //                   and normalised into a caption plan's input exactly as the image processor does without its resize; a pixel
@@ -8,6 +8,9 @@
 //                   the location bins are de-quantised to frame pixels, every region gets the sum of its tokens'
 //                   log-probabilities and a flag saying whether its own tile owns it.  Token classes come from a table in device
 //                   memory, so the kernel knows no tokenizer.
+//   3 box parse     the same block per row for the answers of the grounding / detection tasks, "phrase <loc>x4 <loc>x4 phrase
+//                   <loc>x4 ...": every box gets its corners in frame pixels, the columns of its phrase, the two sums of
+//                   log-probabilities (phrase, the box's four location tokens) and the ownership flag.
 //
 // Mode 1 works on the row with its STRIP tokens taken out, which is what transformers does to the decoded text before it applies its
 // pattern `(.+?)(<loc_n>){8}`: from p = 0, e is the smallest index >= p + 1 whose eight tokens e .. e + 7 are all location tokens; the
@@ -16,6 +19,12 @@
 // sequential f32 sum in ascending token order — the bits do not depend on the launch geometry, and a host twin repeats them.
 // Column 0 of a row is the decoder start token and never part of the answer; the row ends in front of the first EOS behind it, and
 // nothing behind that EOS reaches an output.
+//
+// Mode 3 restates transformers' two patterns on the same stripped row, cut into alternating maximal runs of text and location tokens:
+// `[^<]+(?:<loc_n>){4,}` (grammar 0) takes a text run and ALL location tokens behind it when there are four or more, and a box per
+// four of them; where fewer follow, the pattern's next chance starts INSIDE the run's last `<loc_n>` (behind its '<'), so that token
+// leads the next phrase (`lead`: its text counts without the first character); a row that begins with five or more location tokens
+// gives its first one as such a phrase.  `(?:<loc_n>){4,}` (grammar 1) takes every run of four or more, without a phrase.
 #include "omni_internal.h"
 
 #include <limits.h>
@@ -24,7 +33,7 @@
 
 namespace {
 
-constexpr int kMaxTiles = 65536, kMaxR = 65536, kMaxT = 2049, kMaxM = (kMaxT - 1) / 9;
+constexpr int kMaxTiles = 65536, kMaxR = 65536, kMaxT = 2049, kMaxM = (kMaxT - 1) / 9, kMaxB = (kMaxT - 1) / 4;
 constexpr int kStrip = OMNI_OCR_CLASS_STRIP, kHard = OMNI_OCR_CLASS_HARD;      // 0..999: the location bin itself
 
 // ---------------------------------------------------------------------------------------------- mode 0
@@ -79,7 +88,7 @@ int launch_cut(const omni_op_t* op, hipStream_t s) {
 struct ParseArgs {
   const int* ids; const unsigned short* table; const float* logp; const int* cells;
   int* rec; float* sum; int* rows;
-  int n, T, M, table_len, ld_ids, ld_logp, R, eos;
+  int n, T, M, table_len, ld_ids, ld_logp, R, eos, grammar;
 };
 
 __device__ __forceinline__ int wave_min(int v) {
@@ -174,12 +183,121 @@ __global__ __launch_bounds__(64) void region_parse_kernel(ParseArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- mode 3
+// one block of one wave per row; ParseArgs as in mode 1 with M = (T - 1) / 4 box slots and sums of two floats per slot
+__global__ __launch_bounds__(64) void region_boxes_kernel(ParseArgs a) {
+  __shared__ unsigned short cls[kMaxT];        // class of ORIGINAL token j
+  __shared__ unsigned short orig[kMaxT];       // original index of stripped token s
+  __shared__ unsigned short ba[kMaxB], bb[kMaxB], bc[kMaxB], bp[kMaxB];   // box k: first and one-past-last column of its phrase, column of its
+                                                                          // first location token, phrase ordinal | lead << 15
+  __shared__ int found, kept, phrases;
+  const int lane = threadIdx.x, row = blockIdx.x;
+  const int* ids = a.ids + (long long)row * a.ld_ids;
+  int end = a.T;                               // the row is [1, end): in front of the first EOS behind the start token
+  for (int j = 1 + lane; j < a.T; j += 64) {
+    const int id = ids[j];
+    int c = kHard;
+    if (id >= 0 && id < a.table_len) c = min((int)a.table[id], kHard);
+    cls[j] = (unsigned short)c;
+    if (id == a.eos) end = min(end, j);
+  }
+  end = wave_min(end);
+  __syncthreads();
+  int hard = 0;
+  for (int j = 1 + lane; j < end; j += 64) hard |= cls[j] == kHard;
+  hard = wave_or(hard);
+  if (lane == 0) {
+    int s = 0;
+    for (int j = 1; j < end; ++j)
+      if (cls[j] != kStrip) orig[s++] = (unsigned short)j;
+    int i = 0, k = 0, ph = 0, carry = -1;      // stripped index, boxes, phrases, stripped index of a location token left to lead a phrase
+    while (i < s) {
+      const int t = i;
+      while (i < s && cls[orig[i]] >= 1000) ++i;
+      const int at = i;                        // text run [t, at), location run [at, i)
+      while (i < s && cls[orig[i]] < 1000) ++i;
+      const int r = i - at;
+      int p0, p1, b0, nb, lead = 0;            // phrase [p0, p1) and nb boxes from b0, all stripped indices
+      if (a.grammar == 1) {
+        if (r < 4) continue;
+        p0 = p1 = b0 = at; nb = r / 4;
+      } else {
+        const int start = carry >= 0 ? carry : (at > t ? t : -1);
+        if (start >= 0 && r >= 4) { p0 = start; p1 = at; lead = carry >= 0; b0 = at; nb = r / 4; }
+        else if (start < 0 && r >= 5) { p0 = at; p1 = at + 1; lead = 1; b0 = at + 1; nb = (r - 1) / 4; }
+        else { carry = i - 1; continue; }      // (r = 0 only behind the row's last text run: nothing follows)
+        carry = -1;
+      }
+      for (int q = 0; q < nb; ++q, ++k) {      // k < (s / 4) <= M: every box has four location tokens of its own
+        const int first = orig[b0 + 4 * q];
+        ba[k] = p1 > p0 ? orig[p0] : (unsigned short)first;
+        bb[k] = p1 > p0 ? (unsigned short)(orig[p1 - 1] + 1) : (unsigned short)first;
+        bc[k] = (unsigned short)first;
+        bp[k] = (unsigned short)(ph | (lead << 15));
+      }
+      ++ph;
+    }
+    found = k;
+    phrases = ph;
+    kept = 0;
+  }
+  __syncthreads();
+  const int nbox = found;
+  const int* cell = a.cells + (long long)row * 6;
+  for (int k = lane; k < a.M; k += 64) {
+    int* rec = a.rec + ((long long)row * a.M + k) * 16;
+    float* sum = a.sum + ((long long)row * a.M + k) * 2;
+    if (k >= nbox) {
+#pragma unroll
+      for (int t = 0; t < 16; ++t) rec[t] = 0;
+      sum[0] = sum[1] = 0.0f;
+      continue;
+    }
+    const int c0 = ba[k], c1 = bb[k], cloc = bc[k];
+    int cnt = 0, q = 0;
+    float sp = 0.0f, sb = 0.0f;
+    for (int j = c0; j < c1; ++j) {
+      if (cls[j] == kStrip) continue;
+      ++cnt;
+      if (a.logp) sp += a.logp[(long long)row * a.ld_logp + j - 1];
+    }
+    long long v[4] = {0, 0, 0, 0};
+    for (int j = cloc; j < end && q < 4; ++j) {                                  // the walk saw four location tokens from here
+      const int c = cls[j];
+      if (c == kStrip) continue;
+      if (a.logp) sb += a.logp[(long long)row * a.ld_logp + j - 1];
+      v[q] = (long long)(((2 * c + 1) * a.R) / 2000) + cell[q & 1];
+      ++q;
+    }
+    const long long cx = v[0] + v[2], cy = v[1] + v[3];                           // the box centre, doubled
+    const bool own = cx >= cell[2] && (cell[3] == INT_MAX || cx < cell[3]) && cy >= cell[4] && (cell[5] == INT_MAX || cy < cell[5]);
+    rec[0] = row; rec[1] = c0; rec[2] = c1;
+    rec[3] = (int)v[0]; rec[4] = (int)v[1]; rec[5] = (int)v[2]; rec[6] = (int)v[3];
+    rec[7] = cloc; rec[8] = cnt; rec[9] = own; rec[10] = bp[k] & 0x7fff; rec[11] = bp[k] >> 15;
+    rec[12] = rec[13] = rec[14] = rec[15] = 0;
+    sum[0] = sp; sum[1] = sb;
+    if (own) atomicAdd(&kept, 1);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    int* r = a.rows + (long long)row * 4;
+    r[0] = nbox; r[1] = kept; r[2] = hard | (end == a.T ? 2 : 0); r[3] = phrases;
+  }
+}
+
 int parse_cfg(const omni_op_t* op, ParseArgs& a) {
+  const bool boxes = op->i[0] == 3;
   a.n = op->i[1]; a.T = op->i[2]; a.M = op->i[3]; a.table_len = op->i[4];
   a.ld_ids = op->i[5] ? op->i[5] : a.T; a.ld_logp = op->i[6] ? op->i[6] : a.T - 1; a.R = op->i[7]; a.eos = op->i[8];
+  a.grammar = boxes ? op->i[9] : 0;
   OMNI_REQUIRE(a.n >= 1 && a.n <= kMaxTiles, "region_ocr parse: %d rows (i1), 1..%d", a.n, kMaxTiles);
   OMNI_REQUIRE(a.T >= 2 && a.T <= kMaxT, "region_ocr parse: rows of T = %d tokens (i2), 2..%d", a.T, kMaxT);
-  OMNI_REQUIRE(a.M == (a.T - 1) / 9, "region_ocr parse: %d region slots per row (i3), (T - 1) / 9 = %d", a.M, (a.T - 1) / 9);
+  if (boxes) {
+    OMNI_REQUIRE(a.M == (a.T - 1) / 4, "region_ocr boxes: %d box slots per row (i3), (T - 1) / 4 = %d", a.M, (a.T - 1) / 4);
+    OMNI_REQUIRE(a.grammar == 0 || a.grammar == 1, "region_ocr boxes: grammar %d (i9), 0 = phrases with boxes, 1 = boxes only", a.grammar);
+  } else {
+    OMNI_REQUIRE(a.M == (a.T - 1) / 9, "region_ocr parse: %d region slots per row (i3), (T - 1) / 9 = %d", a.M, (a.T - 1) / 9);
+  }
   OMNI_REQUIRE(a.table_len >= 1, "region_ocr parse: a class table of %d entries (i4)", a.table_len);
   OMNI_REQUIRE(a.ld_ids >= a.T && a.ld_logp >= a.T - 1, "region_ocr parse: row strides %d (i5) / %d (i6) below T = %d / T - 1", a.ld_ids, a.ld_logp, a.T);
   OMNI_REQUIRE(a.R >= 1 && a.R <= kMaxR, "region_ocr parse: R = %d (i7), 1..%d", a.R, kMaxR);
@@ -196,27 +314,28 @@ int launch_parse(const omni_op_t* op, hipStream_t s) {
   OMNI_REQUIRE((unsigned long long)a.ids % 4 == 0 && (unsigned long long)a.table % 2 == 0 && (unsigned long long)a.logp % 4 == 0 &&
                (unsigned long long)a.rec % 4 == 0 && (unsigned long long)a.sum % 4 == 0 && (unsigned long long)a.rows % 4 == 0 &&
                (unsigned long long)a.cells % 4 == 0, "region_ocr parse: a pointer is not aligned to its elements");
-  hipLaunchKernelGGL(region_parse_kernel, dim3(a.n), dim3(64), 0, s, a);
+  if (op->i[0] == 3) hipLaunchKernelGGL(region_boxes_kernel, dim3(a.n), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(region_parse_kernel, dim3(a.n), dim3(64), 0, s, a);
   OMNI_HIP_CHECK(hipGetLastError());
   return OMNI_OK;
 }
 
 }  // namespace
 
-// the bytes mode 1 touches behind p0, p1, p2, p4, p5, p6, p7; false for an op whose slots the launcher refuses (capi.hip::op_extents)
+// the bytes modes 1 and 3 touch behind p0, p1, p2, p4, p5, p6, p7; false for an op whose slots the launcher refuses (capi.hip::op_extents)
 bool omni_region_ocr_extents(const omni_op_t* op, long long ext[8]) {
   ParseArgs a{};
   if (parse_cfg(op, a) != OMNI_OK) return false;
   ext[0] = ((long long)(a.n - 1) * a.ld_ids + a.T) * 4;
   ext[1] = (long long)a.table_len * 2;
   ext[2] = ((long long)(a.n - 1) * a.ld_logp + a.T - 1) * 4;
-  ext[4] = (long long)a.n * a.M * 64; ext[5] = (long long)a.n * a.M * 4; ext[6] = (long long)a.n * 16; ext[7] = (long long)a.n * 24;
+  ext[4] = (long long)a.n * a.M * 64; ext[5] = (long long)a.n * a.M * (op->i[0] == 3 ? 8 : 4); ext[6] = (long long)a.n * 16; ext[7] = (long long)a.n * 24;
   return true;
 }
 
 int omni_launch_region_ocr(const omni_op_t* op, hipStream_t s) {
   const int mode = op->i[0];
   if (mode == 0) return launch_cut(op, s);
-  OMNI_REQUIRE(mode == 1, "region_ocr: mode %d (i0), 0 = tile cut, 1 = region parse", mode);
+  OMNI_REQUIRE(mode == 1 || mode == 3, "region_ocr: mode %d (i0), 0 = tile cut, 1 = region parse, 3 = box parse", mode);
   return launch_parse(op, s);
 }

@@ -693,6 +693,20 @@ def region_parse_op(ids_ptr, table_ptr, logp_ptr, cells_ptr, rec_ptr, sum_ptr, r
                      i={0: 1, 1: n, 2: T, 3: ocr_slots(T) if slots is None else slots, 4: table_len, 5: ld_ids, 6: ld_logp, 7: R, 8: eos})
 
 
+def box_slots(T: int) -> int:
+    """box slots per row of T tokens (mode 3): a box is four location tokens"""
+    return (T - 1) // 4
+
+
+def box_parse_op(ids_ptr, table_ptr, logp_ptr, cells_ptr, rec_ptr, sum_ptr, rows_ptr, n, T, table_len, R, eos, grammar, ld_ids=0, ld_logp=0,
+                 slots=None):
+    """mode 3: n rows of T ids (and their log-probabilities, or None) -> box records i32 [n x M, 16], sums f32 [n x M, 2] (phrase,
+    box), counters i32 [n, 4]; grammar 0 = phrases with boxes, 1 = boxes only"""
+    return L.make_op(L.OP_REGION_OCR, L.F32, p=[ids_ptr, table_ptr, logp_ptr, None, rec_ptr, sum_ptr, rows_ptr, cells_ptr],
+                     i={0: L.OCR_MODE_BOXES, 1: n, 2: T, 3: box_slots(T) if slots is None else slots, 4: table_len, 5: ld_ids, 6: ld_logp,
+                        7: R, 8: eos, 9: grammar})
+
+
 def ocr_cells(origins, R: int):
     """The cells table of mode 1 for tiles of R x R pixels at `origins` [(x, y)] (a grid: every x with every y), one row per tile:
     [origin x, origin y, lo x, hi x, lo y, hi y].  Per axis the boundary between neighbouring tiles is the midpoint of their overlap,
@@ -2270,6 +2284,123 @@ class Florence2Captioner:
             with torch.cuda.stream(self.stream):
                 out = SimpleNamespace(origins=origins, records=rec[:, :M].cpu(), sums=sums[:, :M].cpu(), rows=rows.cpu(), ids=ids.cpu().long(),
                                       logp=logp[:, 1:].cpu())
+        return out
+
+    # ---- box answers and region prompts over tiles (OMNI_OP_REGION_OCR modes 0 and 3)
+    def _check_frame_rows(self, image_u8, prompts, max_new_tokens, controls):
+        """the argument checks `decode_tiles` and `locate_regions` share -> (prompt rows as int lists, checked controls)"""
+        rows = [[int(t) for t in (r.tolist() if isinstance(r, torch.Tensor) else r)] for r in (prompts if prompts is not None else [])]
+        if not rows:
+            raise ValueError("no prompts: at least one prompt row (bos ... eos) is needed")
+        for r in rows:
+            text_capacity(len(r))
+        self.check_max_new(max_new_tokens)
+        controls = self.generation_controls(controls, max_new_tokens, None)
+        if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8 or image_u8.dim() != 3 or image_u8.shape[2] != 3 \
+                or image_u8.shape[0] < 1 or image_u8.shape[1] < 1:
+            raise ValueError("image_u8 must be a uint8 tensor [H, W, 3]")
+        return rows, controls
+
+    @torch.inference_mode()
+    def decode_tiles(self, image_u8: torch.Tensor, origins, prompts, max_new_tokens, controls=None, parse=None, fetch=None):
+        """Greedy answers for windows of a frame, each under its own prompt: one row per (origin, prompt) pair.  The window of
+        R x R pixels (R = the captioner's resolution) at origin (x, y) is cut from the HWC uint8 frame on the device, unscaled, white
+        outside the frame (OMNI_OP_REGION_OCR mode 0); the rows run the chunked greedy decode of `read_regions` (scores plans,
+        `long_plan_rows` rows per chunk, the early-exit poll) with per-row prompts.  prompts: token rows (bos ... eos), as many as
+        origins.  One read-back at the end.  Returns an object with `ids` i64 [rows, T] and `logp` f32 [rows, T - 1] aligned with
+        ids[:, 1:] (T = max_new_tokens + 1; columns no step reached hold the pad token and 0).
+        parse: parse(s, n, cp) is called on the captioner's stream behind the last step of the chunk that holds rows [s, s + n),
+        cp.ids / cp.logp being that chunk's [.., T] buffers — where `locate_regions` launches its parser; fetch: {name: device tensor}
+        read back with the ids, as attributes of the result.
+        ValueError before anything reaches the device: no prompt, a prompt of more than 64 tokens or with an id outside the token
+        table, origins and prompts of different lengths, max_new_tokens outside `check_max_new`, a frame that is not HWC uint8, bad
+        controls."""
+        R = int(self.resolution)
+        rows, controls = self._check_frame_rows(image_u8, prompts, max_new_tokens, controls)
+        origins = [(int(x), int(y)) for x, y in origins]
+        if len(origins) != len(rows):
+            raise ValueError(f"{len(origins)} origins for {len(rows)} prompts: one prompt per origin is needed")
+        if any(abs(v) > 2 ** 30 for o in origins for v in o):
+            raise ValueError("origins must lie within +-2^30")
+        n_all, T = len(rows), max_new_tokens + 1
+        prompt = self.prompt_batch(rows, R)
+        dev = self.device
+        image_u8 = image_u8.to(dev).contiguous()
+        with self._lock:
+            if image_u8.is_cuda:               # a screenshot the caller is still producing on its own stream
+                self.stream.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(self.stream):
+                org = torch.tensor(origins, dtype=torch.int32).to(dev, non_blocking=True)
+                ids = torch.full((n_all, T), int(self.w.pad), dtype=torch.int32, device=dev)     # columns no step reached: pad
+                logp = torch.zeros((n_all, T), dtype=torch.float32, device=dev)
+            at = [0]
+
+            def fill(cp, s, n):
+                at[0] = s
+                self.launch_tiles(cp, n, image_u8, org[s:s + n], self.stream)
+
+            def after(cp, n):
+                s = at[0]
+                if parse is not None:
+                    parse(s, n, cp)
+                done = self.last_steps + 1             # the early exit leaves the columns behind it as `reset` left them
+                ids[s:s + n, :done].copy_(cp.ids[:n, :done], non_blocking=True)
+                logp[s:s + n, :done].copy_(cp.logp[:n, :done], non_blocking=True)
+
+            self._caption_chunks(image_u8, n_all, 128, R, max_new_tokens, None, fill, prompt, True, controls, after=after)
+            with torch.cuda.stream(self.stream):
+                out = SimpleNamespace(ids=ids.cpu().long(), logp=logp[:, 1:].cpu(), **{k: t.cpu() for k, t in (fetch or {}).items()})
+        return out
+
+    @torch.inference_mode()
+    def locate_regions(self, image_u8: torch.Tensor, prompts, class_table, grammar, max_new_tokens=1024, overlap=128, controls=None):
+        """Box answers over the tiles of a screenshot: every prompt of `prompts` (token rows bos ... eos of a Florence-2 task that
+        answers "phrase <loc>x4 ...": <OD>, <DENSE_REGION_CAPTION>, <OPEN_VOCABULARY_DETECTION>, <CAPTION_TO_PHRASE_GROUNDING>, grammar
+        0; or boxes alone: <REGION_PROPOSAL>, grammar 1) is put to every tile of `ScreenParser.tile_origins(W, H, R, R, overlap)`.
+        Rows = prompts x tiles, prompt-major; they are `decode_tiles` rows, and OMNI_OP_REGION_OCR mode 3 parses every chunk's ids and
+        log-probabilities on the device behind its last step.  One read-back at the end.  class_table: as in `read_regions`.
+        Returns an object with per row `origins` [(x, y)], `prompt_index` and `tile_index`, `records` i32 [rows, M, 16], `sums` f32
+        [rows, M, 2], `rows` i32 [rows, 4], `ids` i64 [rows, T] and `logp` f32 [rows, T - 1] (T = max_new_tokens + 1, M = (T - 1) // 4)
+        — the op's outputs as include/omni_amd.h describes them: per box its corners in frame pixels, the columns of its phrase, the
+        phrase's ordinal and `lead`, whether its own tile keeps it (`ocr_cells`), and the log-probability sums of the phrase and of
+        the box's four location tokens; per row the boxes found and kept, the flags (1: re-parse the row from text, 2: cut off at
+        max_new_tokens) and the phrases found.
+        ValueError before anything reaches the device: as `decode_tiles` and `read_regions`, and a grammar outside 0..1."""
+        R = int(self.resolution)
+        if class_table is None:
+            raise ValueError("locate_regions needs class_table (FlorenceProcessor.loc_class_table())")
+        table = check_class_table(class_table)
+        if isinstance(grammar, bool) or grammar not in (0, 1):
+            raise ValueError(f"grammar must be 0 (phrases with boxes) or 1 (boxes only), got {grammar!r}")
+        if isinstance(overlap, bool) or not isinstance(overlap, int) or not 0 <= overlap < R:
+            raise ValueError(f"overlap must be an integer in 0..{R - 1} (tiles are {R} x {R}), got {overlap!r}")
+        prompts, _ = self._check_frame_rows(image_u8, prompts, max_new_tokens, controls)
+        self.prompt_batch(prompts, R)                      # (an id outside the token table)
+        from .pipeline import ScreenParser
+        H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
+        tiles = ScreenParser.tile_origins(W, H, R, R, overlap)[0]
+        origins = list(tiles) * len(prompts)
+        prompt_index = [p for p in range(len(prompts)) for _ in tiles]
+        tile_index = list(range(len(tiles))) * len(prompts)
+        n_all, T = len(origins), max_new_tokens + 1
+        M = box_slots(T)
+        dev = self.device
+        with self._lock:
+            with torch.cuda.stream(self.stream):
+                cells = torch.tensor(ocr_cells(origins, R), dtype=torch.int32).to(dev, non_blocking=True)
+                tab = table.to(dev, non_blocking=True)
+                rec = torch.zeros((n_all, max(M, 1), 16), dtype=torch.int32, device=dev)
+                sums = torch.zeros((n_all, max(M, 1), 2), dtype=torch.float32, device=dev)
+                rows = torch.zeros((n_all, 4), dtype=torch.int32, device=dev)
+
+            def parse(s, n, cp):
+                L.launch(box_parse_op(cp.ids.data_ptr(), tab.data_ptr(), cp.logp.data_ptr() + 4, cells[s:s + n].data_ptr(),
+                                      rec[s:s + n].data_ptr(), sums[s:s + n].data_ptr(), rows[s:s + n].data_ptr(), n, T, tab.numel(), R,
+                                      int(self.w.eos), int(grammar), ld_ids=T, ld_logp=T), self.stream)
+
+            out = self.decode_tiles(image_u8, origins, [prompts[p] for p in prompt_index], max_new_tokens, controls, parse=parse,
+                                    fetch={"records": rec[:, :M], "sums": sums[:, :M], "rows": rows})
+        out.origins, out.prompt_index, out.tile_index = origins, prompt_index, tile_index
         return out
 
     # ---- teacher-forced scoring of given texts (OMNI_OP_GREEDY_STEP p5)

@@ -303,6 +303,11 @@ class ScreenParser:
         embeddings) the elements that look like it, [{"index", "score"}] by descending cosine similarity"""
         return U.match_elements(frame, elements, {"model": self.cap, "processor": self.proc}, exemplars, top_k=top_k)
 
+    def locate(self, frame: torch.Tensor, phrases, task="<OPEN_VOCABULARY_DETECTION>", **kw):
+        """`util.utils.locate` for a frame already on the device: boxes in frame pixels for every phrase (None for the box tasks
+        without text), [{"label", "query", "bbox", "confidence", "tile", "phrase"}]"""
+        return U.locate(frame, {"model": self.cap, "processor": self.proc}, task=task, text=phrases, **kw)
+
     def track(self, prev_frame: torch.Tensor, prev_elements, frame: torch.Tensor, elements, min_score=0.9):
         """`util.utils.track_elements` of two frames already on the device: [(prev_index, index, score)], the one-to-one mutual
         best matches between the elements of the previous frame and of this one"""

@@ -9,6 +9,8 @@ unchanged — plus what a GPU service needs and the reference lacks (SURVEY §8(
   detector graph + packed caption micro-batches (`pipeline.ScreenParser.parse_batch`), PNG decode and the
   overlay + PNG encode of each image run on a host thread pool; response = {results: [<single-image schema>],
   latency};
+* `POST /locate/ {base64_image, phrases, task?}` -> {boxes, latency}: where the phrases are, in frame pixels, from the caption
+  model's box tasks over tiles (`util.utils.locate`); a bad request (unknown task, no phrase, no tokenizer) is a 422;
 * OCR is not part of the hot path: a request may carry `ocr: {"texts": [...], "boxes": [[x0,y0,x1,y1] px]}`
   per image (never stored on the shared parser — requests are concurrent).
 """
@@ -47,6 +49,11 @@ class ParseService:
         start = time.time()
         som_image, parsed = self.parser.parse(base64_image, ocr=_ocr_tuple(ocr))
         return {"som_image_base64": som_image, "parsed_content_list": parsed, "latency": time.time() - start}
+
+    def locate_one(self, base64_image: str, phrases, task: Optional[str] = None) -> dict:
+        start = time.time()
+        boxes = self.parser.locate(base64_image, phrases, **({"task": task} if task else {}))
+        return {"boxes": boxes, "latency": time.time() - start}
 
     # ---- batch: device batching for equal-sized frames
     def screen_parser(self):
@@ -132,6 +139,11 @@ def build_app(config, service: Optional[ParseService] = None):
     class BatchRequest(BaseModel):
         images: List[ParseRequest]
 
+    class LocateRequest(BaseModel):
+        base64_image: str
+        phrases: Optional[List[str]] = None
+        task: Optional[str] = None
+
     @app.post("/parse/")
     def parse(req: ParseRequest):
         try:
@@ -143,6 +155,13 @@ def build_app(config, service: Optional[ParseService] = None):
     def parse_batch(req: BatchRequest):
         try:
             return svc.parse_many([{"base64_image": r.base64_image, "ocr": r.ocr} for r in req.images])
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+
+    @app.post("/locate/")
+    def locate(req: LocateRequest):
+        try:
+            return svc.locate_one(req.base64_image, req.phrases, req.task)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 

@@ -170,6 +170,13 @@ class Omniparser(object):
         rankings = U.rank_elements(np.asarray(image.convert("RGB")), elements, self.caption_model_processor, queries, top_k=top_k)
         return elements, rankings
 
+    def locate(self, image_base64: str, phrases, **kw):
+        """`utils.locate` of the screenshot: where are `phrases` (a phrase or a list; None for the box tasks without text,
+        task=...)?  Boxes in frame pixels, [{"label", "query", "bbox", "confidence", "tile", "phrase"}], from the caption model alone
+        — no detector, no OCR engine.  kw: `utils.locate`'s (task, max_new_tokens, overlap, min_confidence, banned_phrases,
+        generation, return_stats)."""
+        return U.locate(np.asarray(decode_image(image_base64).convert("RGB")), self.caption_model_processor, text=phrases, **kw)
+
     def find_similar(self, image_base64: str, exemplars_base64, top_k=5):
         """`parse`, then `utils.match_elements` of the parsed elements against exemplar images (base64, as the screenshot is):
         (parsed_content_list, per exemplar the top_k elements as {"index", "score"} by descending cosine similarity of the caption

@@ -67,7 +67,15 @@ TASK_PROMPTS = {
     "<DENSE_REGION_CAPTION>": "Locate the objects in the image, with their descriptions.",
     "<REGION_PROPOSAL>": "Locate the region proposals in the image.",
 }
-# task tokens whose sentence embeds an {input} (grounding / region tasks): refused — their answers are location tokens nobody here decodes
+# task tokens whose sentence embeds an {input}: `prompt_ids` refuses them (it has no input to put in); `task_prompt_ids` builds them
+TASK_PROMPTS_WITH_INPUT = {
+    "<CAPTION_TO_PHRASE_GROUNDING>": "Locate the phrases in the caption: {input}",
+    "<OPEN_VOCABULARY_DETECTION>": "Locate {input} in the image.",
+    "<REGION_TO_CATEGORY>": "What is the region {input}?",
+    "<REGION_TO_DESCRIPTION>": "What does the region {input} describe?",
+    "<REGION_TO_OCR>": "What text is in the region {input}?",
+}
+TASKS_WITH_REGION = ("<REGION_TO_CATEGORY>", "<REGION_TO_DESCRIPTION>", "<REGION_TO_OCR>")
 TASKS_WITH_INPUT = ("<CAPTION_TO_PHRASE_GROUNDING>", "<REFERRING_EXPRESSION_SEGMENTATION>", "<REGION_TO_SEGMENTATION>",
                     "<OPEN_VOCABULARY_DETECTION>", "<REGION_TO_CATEGORY>", "<REGION_TO_DESCRIPTION>", "<REGION_TO_OCR>")
 
@@ -142,6 +150,41 @@ class FlorenceProcessor:
             where = Path(self.model_dir) / "tokenizer.json" if self.model_dir is not None else "tokenizer.json (no model directory was given)"
             raise ValueError(f"the prompt {text!r} needs a tokenizer: {where} is missing (only the default <CAPTION> prompt works without it)")
         return [self.bos_id] + list(self.tok.encode(text, add_special_tokens=False).ids) + [self.eos_id]
+
+    @staticmethod
+    def quantize_box(box, size):
+        """location bins [x0, y0, x1, y1] of a box in pixels of an image of `size` (width, height): transformers'
+        Florence2PostProcessor.quantize on an f32 tensor — floor(f32(v) / f32(size / 1000)) in f32 arithmetic, clamped to 0..999.
+        (Not v * 1000 // size: f32(0.064) lies above 0.064, so 8 px of 64 fall into bin 124, not 125.)"""
+        w, h = size
+        per = (np.float32(w / 1000), np.float32(h / 1000))
+        return [int(min(max(np.floor(np.float32(v) / per[k & 1]), 0), 999)) for k, v in enumerate(box)]
+
+    def task_prompt_ids(self, task, text=None, region=None, size=None):
+        """token ids (bos ... eos) of the prompt of a Florence-2 task WITH an input, the sentence transformers' processor builds
+        (`_construct_prompts`: the input stripped and put into the task's sentence, TASK_PROMPTS_WITH_INPUT):
+        <OPEN_VOCABULARY_DETECTION> and <CAPTION_TO_PHRASE_GROUNDING> take `text`; <REGION_TO_CATEGORY>, <REGION_TO_DESCRIPTION> and
+        <REGION_TO_OCR> take `region`, a box [x0, y0, x1, y1] in pixels of an image of `size` (width, height), written as the four
+        location tokens `quantize_box` gives.  Needs the tokenizer.json next to the checkpoint.  ValueError: another task (the
+        polygon tasks included), the wrong kind of input for the task, no tokenizer."""
+        if task not in TASK_PROMPTS_WITH_INPUT:
+            raise ValueError(f"task {task!r} is not a task with an input this captioner supports ({', '.join(TASK_PROMPTS_WITH_INPUT)})")
+        if task in TASKS_WITH_REGION:
+            if text is not None or region is None or size is None:
+                raise ValueError(f"task {task} takes a region (box in pixels) and the size of its image, no text")
+            box = [float(v) for v in region]
+            if len(box) != 4 or len(tuple(size)) != 2 or min(size) <= 0:
+                raise ValueError("a region is [x0, y0, x1, y1] in pixels of an image of size (width, height)")
+            given = "".join(f"<loc_{b}>" for b in self.quantize_box(box, size))
+        else:
+            if not isinstance(text, str) or region is not None:
+                raise ValueError(f"task {task} takes a text, no region")
+            given = text.replace(task, "").strip()
+        sentence = TASK_PROMPTS_WITH_INPUT[task].format(input=given)
+        if self.tok is None:
+            where = Path(self.model_dir) / "tokenizer.json" if self.model_dir is not None else "tokenizer.json (no model directory was given)"
+            raise ValueError(f"the prompt {sentence!r} needs a tokenizer: {where} is missing")
+        return [self.bos_id] + list(self.tok.encode(sentence, add_special_tokens=False).ids) + [self.eos_id]
 
     def loc_class_table(self):
         """(class table u16 [vocab] as numpy, per-token texts) for OMNI_OP_REGION_OCR and `parse_ocr_regions`, built once from the
@@ -702,6 +745,232 @@ class FlorenceOCR:
     def __call__(self, pil_image):
         regions = self.read(pil_image)
         return [r["text"] for r in regions], [r["bbox"] for r in regions]
+
+
+# ------------------------------------------------------------------------------------------ grounding: box answers and region prompts
+_BOX_TASKS = {"<OD>": 0, "<DENSE_REGION_CAPTION>": 0, "<REGION_PROPOSAL>": 1,          # task -> grammar of OMNI_OP_REGION_OCR mode 3
+              "<OPEN_VOCABULARY_DETECTION>": 0, "<CAPTION_TO_PHRASE_GROUNDING>": 0}
+_PHRASE_PATTERNS = (r"[^<]+(?:<loc_\d+>){4,}", r"(?:<loc_\d+>){4,}")                      # grammar 0 / 1: transformers' phrase patterns
+_PHRASE_TEXT = r"^\s*(.*?)(?=<od>|</od>|<box>|</box>|<bbox>|</bbox>|<loc_)"
+_BOX_PATTERN = r"<loc_(\d+)>" * 4
+
+
+def _answer_text(ids_row, processor):
+    """(text, owner): the row's tokens in front of the first EOS behind column 0 rendered one by one (`loc_class_table` texts) with
+    `<s>`, `</s>`, `<pad>` deleted as str.replace deletes them, and per character the column of `ids_row` it came from"""
+    _table, texts = processor.loc_class_table()
+    row = [int(t) for t in (ids_row.tolist() if hasattr(ids_row, "tolist") else ids_row)]
+    end = next((j for j in range(1, len(row)) if row[j] == processor.eos_id), len(row))
+    text, owner = "", []
+    for j in range(1, end):
+        t = texts[row[j]] if 0 <= row[j] < len(texts) else ""
+        text += t
+        owner += [j] * len(t)
+    for needle in ("<s>", "</s>", "<pad>"):
+        at = text.find(needle)
+        while at >= 0:
+            text = text[:at] + text[at + len(needle):]
+            del owner[at:at + len(needle)]
+            at = text.find(needle, at)
+    return text, owner
+
+
+def parse_box_answer(ids_row, processor, size, grammar):
+    """The answer of ONE image to a task that replies "phrase <loc>x4 ..." parsed on the host FROM ITS TEXT, as transformers'
+    Florence2PostProcessor parses it: grammar 0 is parse_description_with_bboxes_from_text_and_spans (and, but for its banned
+    phrases, parse_phrase_grounding_from_text_and_spans), grammar 1 the same with allow_empty_phrase (<REGION_PROPOSAL>).  The device
+    parses tokens instead (OMNI_OP_REGION_OCR mode 3) and flags the rows in which that can differ; this is what those rows fall
+    back to.  ids_row, size: as in `parse_ocr_regions`.
+    -> one entry per box, in the answer's order: {"label": the phrase, stripped, non-ASCII characters dropped, "raw_label": before
+    they are dropped, "bbox" [x0, y0, x1, y1] in pixels of the image, "phrase": the ordinal of its phrase among those that gave
+    boxes, "phrase_columns" / "box_columns": the columns of `ids_row` whose text the phrase / the box covers}"""
+    import re
+    if isinstance(grammar, bool) or grammar not in (0, 1):
+        raise ValueError(f"grammar must be 0 (phrases with boxes) or 1 (boxes only), got {grammar!r}")
+    text, owner = _answer_text(ids_row, processor)
+    w, h = size
+    out, ordinal = [], 0
+    for m in re.finditer(_PHRASE_PATTERNS[grammar], text):
+        chunk, own = m.group(0), owner[m.start():m.end()]
+        for needle in ("<ground>", "<obj>"):                # str.replace(needle, "", 1)
+            at = chunk.find(needle)
+            if at >= 0:
+                chunk = chunk[:at] + chunk[at + len(needle):]
+                del own[at:at + len(needle)]
+        if not chunk and grammar == 0:
+            continue
+        pm = re.search(_PHRASE_TEXT, chunk)
+        if not pm:
+            continue
+        boxes = list(re.finditer(_BOX_PATTERN, chunk))
+        if not boxes:
+            continue
+        raw = pm.group().strip()
+        first_loc = chunk.find("<loc_")
+        for b in boxes:
+            bins = [int(g) for g in b.groups()]
+            out.append({"label": raw.encode("ascii", "ignore").decode("ascii"), "raw_label": raw,
+                        "bbox": [dequantize_bin(v, h if k & 1 else w) for k, v in enumerate(bins)], "phrase": ordinal,
+                        "phrase_columns": sorted(set(own[:max(first_loc, 0)])), "box_columns": sorted(set(own[b.start():b.end()]))})
+        ordinal += 1
+    return out
+
+
+def _box_tasks_check(task, text):
+    """(grammar, queries): the phrases a box task is asked with, [None] for the tasks without an input"""
+    if task not in _BOX_TASKS:
+        raise ValueError(f"locate: task {task!r} does not answer in boxes ({', '.join(_BOX_TASKS)})")
+    with_input = task in TASKS_WITH_INPUT
+    if not with_input:
+        if text is not None:
+            raise ValueError(f"task {task} takes no text")
+        return _BOX_TASKS[task], [None]
+    queries = [text] if isinstance(text, str) else list(text) if text is not None else []
+    if not queries or not all(isinstance(q, str) and q.strip() for q in queries):
+        raise ValueError(f"task {task} needs a phrase or a list of phrases")
+    return _BOX_TASKS[task], queries
+
+
+@torch.inference_mode()
+def locate(image_source, caption_model_processor, task="<OPEN_VOCABULARY_DETECTION>", text=None, max_new_tokens=256, overlap=128,
+           min_confidence=0.0, banned_phrases=(), generation=None, return_stats=False):
+    """Where is it?  Boxes in frame pixels from the caption model's own box tasks — `Florence2Captioner.locate_regions`: every
+    phrase is put to every native-resolution tile of the frame (cut on the device, `overlap` pixels shared between neighbours),
+    decoded greedily, and the answers "phrase <loc>x4 ..." are parsed on the device.
+    task: <OPEN_VOCABULARY_DETECTION> or <CAPTION_TO_PHRASE_GROUNDING> with `text`, a phrase or a list of phrases (one decode row
+    per phrase and tile); <OD>, <DENSE_REGION_CAPTION> or <REGION_PROPOSAL> (boxes without labels) with text=None.
+    -> [{"label", "query", "bbox" [x0, y0, x1, y1] in frame pixels, "confidence", "tile", "phrase"}], query by query, tile by tile,
+    in the answer's order within a tile.  label: the phrase the model wrote in front of the box, stripped, non-ASCII characters
+    dropped (for phrase grounding a phrase in `banned_phrases` is dropped with its boxes, as transformers drops
+    banned_grounding_tokens); query: the phrase asked for (None for the tasks without text); phrase: the ordinal of the label's
+    phrase in its row — the boxes of one phrase share it.  A box seen by two overlapping tiles is returned by the tile whose cell
+    holds its centre (`florence.ocr_cells`), as in `read_text_regions`.  confidence = exp((log-probability sum of the phrase's tokens
+    + that of the box's four location tokens) / (phrase tokens + 4)); boxes below `min_confidence` are dropped.  Rows the device
+    flags as holding a token it does not parse are re-parsed from their text by `parse_box_answer`; an <OPEN_VOCABULARY_DETECTION>
+    row that answers with polygons (`<poly>`) yields no boxes.
+    return_stats=True: (boxes, per row {"query", "tile", "found", "kept", "phrases", "truncated", "fallback", "polygons"}).
+    ValueError before anything reaches the device: an unknown task, text missing or given to a task without one, no tokenizer.json,
+    min_confidence outside 0..1, and `locate_regions`' own."""
+    import math
+    from ..florence import ocr_cells
+    model, processor = caption_model_processor["model"], caption_model_processor["processor"]
+    grammar, queries = _box_tasks_check(task, text)
+    if isinstance(min_confidence, bool) or not isinstance(min_confidence, (int, float)) or not 0.0 <= min_confidence <= 1.0:
+        raise ValueError(f"min_confidence must be a number in 0..1, got {min_confidence!r}")
+    banned = set(banned_phrases) if task == "<CAPTION_TO_PHRASE_GROUNDING>" else set()
+    table, texts = processor.loc_class_table()
+    prompts = [processor.prompt_ids(task) if q is None else processor.task_prompt_ids(task, text=q) for q in queries]
+    if isinstance(image_source, str):
+        image_source = Image.open(image_source)
+    if isinstance(image_source, Image.Image):
+        image_source = np.asarray(image_source.convert("RGB"))
+    out = model.locate_regions(_frame_on(image_source, model.device), prompts, table, grammar, max_new_tokens=max_new_tokens, overlap=overlap,
+                               controls=generation)
+    R = int(model.resolution)
+    cells = ocr_cells(out.origins, R)
+    found_boxes, stats = [], []
+    for r, (ox, oy) in enumerate(out.origins):
+        found, kept, flags, phrases = (int(v) for v in out.rows[r, :4])
+        ids = out.ids[r].tolist()
+        cands, poly = [], False                             # (raw label, label, bbox, log-probability sum, tokens, own, phrase ordinal)
+        if flags & 1:                                       # from the text, on the host
+            poly = task == "<OPEN_VOCABULARY_DETECTION>" and "<poly>" in _answer_text(ids, processor)[0]
+            for g in ([] if poly else parse_box_answer(ids, processor, (R, R), grammar)):
+                box = [g["bbox"][0] + ox, g["bbox"][1] + oy, g["bbox"][2] + ox, g["bbox"][3] + oy]
+                cols = g["phrase_columns"] + g["box_columns"]
+                own = _owns(cells[r], [box[0], box[1], box[2], box[3]])
+                cands.append((g["raw_label"], g["label"], box, float(sum(float(out.logp[r, j - 1]) for j in cols)), len(cols), own, g["phrase"]))
+            found, kept, phrases = len(cands), sum(1 for c in cands if c[5]), len({c[6] for c in cands})
+        else:
+            for k in range(found):
+                rec = out.records[r, k].tolist()
+                toks = [texts[t] for t in ids[rec[1]:rec[2]] if table[t] != L.OCR_CLASS_STRIP]
+                if rec[11] and toks:
+                    toks[0] = toks[0][1:]
+                raw = "".join(toks).strip()
+                cands.append((raw, raw.encode("ascii", "ignore").decode("ascii"), rec[3:7], float(out.sums[r, k, 0]) + float(out.sums[r, k, 1]),
+                              rec[8] + 4, bool(rec[9]), rec[10]))
+        q = queries[out.prompt_index[r]]
+        stats.append({"query": q, "tile": out.tile_index[r], "found": found, "kept": kept, "phrases": phrases, "truncated": bool(flags & 2),
+                      "fallback": bool(flags & 1), "polygons": poly})
+        for raw, label, box, total, count, own, ordinal in cands:
+            conf = math.exp(total / count)
+            if own and raw not in banned and conf >= min_confidence:
+                found_boxes.append({"label": label, "query": q, "bbox": [int(v) for v in box], "confidence": conf, "tile": out.tile_index[r],
+                                    "phrase": ordinal})
+    return (found_boxes, stats) if return_stats else found_boxes
+
+
+def ground_elements(image_source, elements, caption_model_processor, phrases, min_iou=0.5, **locate_kw):
+    """Which parsed element is "the Save button"?  `locate` for every phrase, and for each located box the element of `elements` (a
+    `parsed_content_list` with ratio bboxes) it overlaps best.  On the host, with the box helpers of the overlap filter.
+    -> per phrase a list of locate's boxes, each with "element": the index of the element with the largest IoU (ties: the lower
+    index), or -1 when that IoU is below `min_iou`, and "iou": that IoU."""
+    if isinstance(min_iou, bool) or not isinstance(min_iou, (int, float)) or not 0.0 <= min_iou <= 1.0:
+        raise ValueError(f"min_iou must be a number in 0..1, got {min_iou!r}")
+    phrases = [phrases] if isinstance(phrases, str) else list(phrases)
+    locate_kw.setdefault("task", "<OPEN_VOCABULARY_DETECTION>")
+    if locate_kw.get("return_stats"):
+        raise ValueError("ground_elements returns boxes only: return_stats is not supported")
+    if isinstance(image_source, str):
+        image_source = Image.open(image_source)
+    if isinstance(image_source, Image.Image):
+        image_source = np.asarray(image_source.convert("RGB"))
+    H, W = image_source.shape[0], image_source.shape[1]
+    boxes = locate(image_source, caption_model_processor, text=phrases, **locate_kw)
+    px = [[e["bbox"][0] * W, e["bbox"][1] * H, e["bbox"][2] * W, e["bbox"][3] * H] for e in elements]
+    out = [[] for _ in phrases]
+    for b in boxes:
+        best, best_iou = -1, 0.0
+        for k, e in enumerate(px):
+            it = _inter(b["bbox"], e)
+            union = _area(b["bbox"]) + _area(e) - it
+            iou = it / union if union > 0 else 0.0
+            if iou > best_iou:
+                best, best_iou = k, iou
+        out[phrases.index(b["query"])].append({**b, "element": best if best_iou >= min_iou else -1, "iou": best_iou})
+    return out
+
+
+@torch.inference_mode()
+def describe_regions(image_source, boxes_px, caption_model_processor, task="<REGION_TO_DESCRIPTION>", max_new_tokens=64, overlap=128,
+                     generation=None):
+    """What is in this box, seen in its surroundings?  Florence-2's region tasks (<REGION_TO_DESCRIPTION>, <REGION_TO_CATEGORY>,
+    <REGION_TO_OCR>) on native-resolution tiles: each box [x0, y0, x1, y1] in frame pixels goes to the tile of
+    `ScreenParser.tile_origins(W, H, R, R, overlap)` whose cell (`florence.ocr_cells`) holds its centre, is clipped to that tile and
+    written into the prompt as four location tokens quantised in tile coordinates (`FlorenceProcessor.task_prompt_ids`); one decode
+    row per box (`Florence2Captioner.decode_tiles`).  -> the texts, `batch_decode`d and stripped, one per box.
+    ValueError before anything reaches the device: another task, a box that is not four numbers with x0 <= x1 and y0 <= y1, no
+    tokenizer.json, and `decode_tiles`' own."""
+    from ..florence import ocr_cells
+    from ..pipeline import ScreenParser
+    model, processor = caption_model_processor["model"], caption_model_processor["processor"]
+    if task not in ("<REGION_TO_DESCRIPTION>", "<REGION_TO_CATEGORY>", "<REGION_TO_OCR>"):
+        raise ValueError(f"describe_regions: task {task!r} takes no region (<REGION_TO_DESCRIPTION>, <REGION_TO_CATEGORY>, <REGION_TO_OCR>)")
+    R = int(model.resolution)
+    if isinstance(overlap, bool) or not isinstance(overlap, int) or not 0 <= overlap < R:
+        raise ValueError(f"overlap must be an integer in 0..{R - 1} (tiles are {R} x {R}), got {overlap!r}")
+    boxes = [[float(v) for v in b] for b in boxes_px]
+    if any(len(b) != 4 or not (b[0] <= b[2] and b[1] <= b[3]) for b in boxes):
+        raise ValueError("a box is [x0, y0, x1, y1] in frame pixels with x0 <= x1 and y0 <= y1")
+    if not boxes:
+        return []
+    if isinstance(image_source, str):
+        image_source = Image.open(image_source)
+    if isinstance(image_source, Image.Image):
+        image_source = np.asarray(image_source.convert("RGB"))
+    H, W = image_source.shape[0], image_source.shape[1]
+    tiles = ScreenParser.tile_origins(W, H, R, R, overlap)[0]
+    cells = ocr_cells(tiles, R)
+    origins, prompts = [], []
+    for b in boxes:
+        k = next(k for k, c in enumerate(cells) if _owns(c, [b[0], b[1], b[2], b[3]]))     # the cells partition the plane
+        ox, oy = tiles[k]
+        region = [min(max(b[0] - ox, 0), R), min(max(b[1] - oy, 0), R), min(max(b[2] - ox, 0), R), min(max(b[3] - oy, 0), R)]
+        origins.append((ox, oy))
+        prompts.append(processor.task_prompt_ids(task, region=region, size=(R, R)))
+    out = model.decode_tiles(_frame_on(image_source, model.device), origins, prompts, max_new_tokens, controls=generation)
+    return [t.strip() for t in processor.batch_decode(out.ids, skip_special_tokens=True)]
 
 
 @torch.inference_mode()
