@@ -472,9 +472,48 @@ enum {
    *    p5 sums f32[i1 x M, 2] {logp over the phrase's n_content tokens, logp over the box's four location tokens}, each added in
    *    ascending column order (0 with p2 = NULL and in unused slots)
    *    p6 rows i32[i1, 4] {boxes found, boxes kept, flags, phrases found}
-   * OMNI_E_ARG (nothing launched, nothing written): any value outside its range, M != (T - 1) / 9 (mode 3: (T - 1) / 4), a grammar
-   * outside 0..1, any other i0, a NULL pointer other than p2, a misaligned pointer.  The pointer check covers exactly these extents.
-   * The op's dtype matters to mode 0 only.  Plan bundles and the model-level entry points do not use it. */
+   *  i0 = 5, polygon parse (region_polys_kernel, one 64-lane block per row): the answers of the segmentation tasks
+   *    (<REFERRING_EXPRESSION_SEGMENTATION>, <REGION_TO_SEGMENTATION>), transformers' "polygons" post-processing with
+   *    allow_empty_phrase.  The row, the cells, the flags, p0 .. p2 and i4 .. i8 as in mode 1, except:
+   *    i2 = T (3..2049)   i3 = P, polygon slots per row: exactly T / 2   i9 = V, vertex slots per row: exactly (T - 1) / 2
+   *    classes: OMNI_OCR_CLASS_SEP (<sep>), OMNI_OCR_CLASS_POLY (<poly>) and OMNI_OCR_CLASS_POLY_END (</poly>) count here (modes 1
+   *    and 3 take them as HARD); values above OMNI_OCR_CLASS_POLY_END and ids outside 0..i4-1 count as HARD.
+   *    STRUCTURE tokens are the location bins, SEP, POLY and POLY_END.  A run is a maximal sequence of at least 4 structure tokens of
+   *    the row's non-STRIP tokens (TEXT and HARD only separate runs); shorter sequences give nothing.  A run gives nothing unless a
+   *    location bin or POLY stands in it, looking behind ONE leading location bin when it starts with one.  A run that holds both POLY
+   *    and POLY_END gives the instances POLY content POLY_END, left to right without overlap: the first POLY, up to the next POLY_END,
+   *    on behind it (no such pair: nothing); any other run is one instance whose content is the run.  In a content, every maximal
+   *    sequence of location bins that SEP follows or that ends the content is a polygon (one that POLY or POLY_END follows is not);
+   *    an odd number of bins drops the last, so a polygon may have 0 vertices; an instance without a polygon is dropped and not
+   *    counted.  Vertex q of a polygon is ((2 bin + 1) R) / 2000 + origin from bins 2q (x) and 2q + 1 (y).
+   *    p3 vertices i32[i1, V, 2] {x, y} in frame pixels: the row's vertices in answer order, polygon after polygon; unused slots zero
+   *    p4 records i32[i1 x P, 16], polygon k of row r at slot r P + k: {r, instance ordinal, polygon ordinal within the instance, v0,
+   *    nv, c0, c1, n_loc, kept, run ordinal, bx0, by0, bx1, by1, 0, 0}: v0 the polygon's first vertex slot, nv its vertices, c0 / c1 the
+   *    ORIGINAL columns of its first location token and one past its last (a dropped odd one included), n_loc its location tokens,
+   *    run the ordinal of its run among the row's runs, bx0 .. by1 the bounding box over ALL vertices of the instance (zeros without
+   *    one), kept = the instance has a vertex and (bx0 + bx1, by0 + by1) lies in the row's cell on both axes.  Unused slots are zero.
+   *    p5 sums f32[i1 x P]: logp over the 2 nv tokens that made the polygon's vertices, added in ascending column order (0 with p2 =
+   *    NULL and in unused slots)
+   *    p6 rows i32[i1, 4] {polygons found, instances found, flags, instances kept}
+   *  i0 = 6, mask raster (poly_mask_kernel, one wave per pixel row, four pixel rows per block): mode 5's outputs, read where it left
+   *    them, become bit masks.  i1 = rows  i2 = T as in mode 5 (P and V follow from it)  i3 = I, instance slots per row (1..64)
+   *    i4 = H  i5 = W of the frame  i7 = R
+   *    p0 mode 5's records   p1 its rows   p2 its vertices   p7 the cells (their origins are read)
+   *    p4 masks u32[i1, I, R, (R + 31) / 32], TILE-LOCAL: bit b of word w of pixel row y is tile pixel x = 32 w + b
+   *    p5 counts i32[i1, I, R]: set bits per pixel row
+   *    Pixel (x, y) of slot s is set when x < R, the frame pixel (origin x + x, origin y + y) lies in [0, W) x [0, H), the instance
+   *    with ordinal s is kept, and the pixel's centre lies inside at least one of its polygons with nv >= 3, even-odd per polygon.
+   *    In tile-local doubled coordinates and 64-bit integers, centre P = (2x + 1, 2y + 1) and vertices 2 v: edge a -> b (the last
+   *    vertex to the first included) counts when (ay > Py) != (by > Py) and (Px - ax)(by - ay) < (Py - ay)(bx - ax) for by > ay, >
+   *    otherwise; inside = an odd count.  Slots without an instance, instances that are not kept and bits x >= R are zero; every
+   *    word and count is written, nothing is accumulated.  An instance's vertices (at most 1024) are staged in LDS.
+   *    p0 .. p2 must be what mode 5 wrote for the same i1, T, R and cells: the records of an instance consecutive, its vertices
+   *    consecutive and inside the tile.  With other contents no access leaves the extents, but the masks are unspecified.
+   * i0 = 2 and i0 = 4 stay refused: the argument tests of modes 1 and 3 launch them with those modes' slots and expect OMNI_E_ARG.
+   * OMNI_E_ARG (nothing launched, nothing written): any value outside its range, M != (T - 1) / 9 (mode 3: (T - 1) / 4; mode 5: P !=
+   * T / 2 or V != (T - 1) / 2), a grammar outside 0..1, any other i0, a NULL pointer other than p2 of modes 1, 3 and 5, a misaligned
+   * pointer.  The pointer check covers exactly these extents.  The op's dtype matters to mode 0 only.  Plan bundles and the
+   * model-level entry points do not use it. */
   OMNI_OP_REGION_OCR = OMNI_OP_VISUAL_MATCH + 1,   /* 29 (spelled like the three kinds above) */
   OMNI_OP__END
 };
@@ -483,6 +522,10 @@ enum {
 #define OMNI_OCR_CLASS_STRIP 1000
 #define OMNI_OCR_CLASS_TEXT 1001
 #define OMNI_OCR_CLASS_HARD 1002
+/* mode 5 alone (modes 1 and 3 clamp them to HARD): <sep>, <poly>, </poly> */
+#define OMNI_OCR_CLASS_SEP 1003
+#define OMNI_OCR_CLASS_POLY 1004
+#define OMNI_OCR_CLASS_POLY_END 1005
 
 /* header of the trie block of OMNI_OP_GREEDY_VOCAB_STEP (p7); first / edge_tok / edge_dst follow it, see the op */
 #define OMNI_VOCAB_HEADER_BYTES 32

@@ -25,7 +25,9 @@ OP_GREEDY_VOCAB_STEP = 27
 OP_VISUAL_MATCH = 28
 OP_REGION_OCR = 29
 OCR_MODE_CUT, OCR_MODE_PARSE, OCR_MODE_BOXES = 0, 1, 3              # OMNI_OP_REGION_OCR's i0 (2 is refused)
+OCR_MODE_POLYS, OCR_MODE_MASKS = 5, 6       # polygon parse, mask raster; 2 and 4 stay refused: the argument tests of modes 1 and 3 launch them
 OCR_CLASS_STRIP, OCR_CLASS_TEXT, OCR_CLASS_HARD = 1000, 1001, 1002      # include/omni_amd.h::OMNI_OCR_CLASS_*
+OCR_CLASS_SEP, OCR_CLASS_POLY, OCR_CLASS_POLY_END = 1003, 1004, 1005    # <sep>, <poly>, </poly>: mode 5 alone, HARD to modes 1 and 3
 CAND_BYTES = 32
 ABI_VERSION = 3         # include/omni_amd.h::OMNI_ABI_VERSION — a library built from other headers is refused at load time
 

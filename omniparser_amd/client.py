@@ -84,6 +84,21 @@ class OmniParserClient:
             raise RuntimeError(f"{url} -> HTTP {resp.status_code}: {getattr(resp, 'text', '')[:200]}")
         return resp.json()["boxes"]
 
+    def segment(self, image: ImageLike, phrases: Optional[Sequence[str]] = None, regions: Optional[Sequence[Sequence[float]]] = None) -> list:
+        """POST /segment/: the shapes of `phrases` or of the boxes `regions` (frame pixels) in the image, [{"query" | "region",
+        "polygons", "bbox", "area", "point", "confidence", ...}]; masks do not travel"""
+        payload = {"base64_image": encode_image(image)}
+        if phrases is not None:
+            payload["phrases"] = list(phrases)
+        if regions is not None:
+            payload["regions"] = [list(b) for b in regions]
+        url = self.url.rstrip("/")
+        url = (url[: -len("/parse")] if url.endswith("/parse") else url) + "/segment/"
+        resp = self._post(url, json=payload)
+        if getattr(resp, "status_code", 200) != 200:
+            raise RuntimeError(f"{url} -> HTTP {resp.status_code}: {getattr(resp, 'text', '')[:200]}")
+        return resp.json()["segments"]
+
     def parse_batch(self, images: Sequence[ImageLike], ocr: Optional[Sequence[Optional[dict]]] = None) -> list:
         b64 = [encode_image(im) for im in images]
         items = [{"base64_image": b} if not (ocr and ocr[i]) else {"base64_image": b, "ocr": ocr[i]} for i, b in enumerate(b64)]

@@ -189,7 +189,7 @@ static void op_extents(const omni_op_t* op, long long ext[8]) {
         if (i[1] > 0 && i[2] > 0 && i[3] > 0 && i[4] > 0 && i[13] > 0) {
           ext[0] = (long long)i[2] * i[3] * 3; ext[1] = (long long)i[1] * 8; ext[4] = (long long)i[1] * i[4] * i[4] * i[13] * esz; ext[7] = 1024;
         }
-      } else if (i[0] == 1 || i[0] == 3) {
+      } else if (i[0] == 1 || i[0] == 3 || i[0] == 5 || i[0] == 6) {
         omni_region_ocr_extents(op, ext);
       }
       break;

@@ -707,6 +707,29 @@ def box_parse_op(ids_ptr, table_ptr, logp_ptr, cells_ptr, rec_ptr, sum_ptr, rows
                         7: R, 8: eos, 9: grammar})
 
 
+def poly_slots(T: int):
+    """(polygon slots, vertex slots) per row of T tokens (mode 5): "<loc> <sep> <loc> <sep> ..." fills the first, a vertex is two
+    location tokens"""
+    return T // 2, (T - 1) // 2
+
+
+def poly_parse_op(ids_ptr, table_ptr, logp_ptr, cells_ptr, verts_ptr, rec_ptr, sum_ptr, rows_ptr, n, T, table_len, R, eos, ld_ids=0, ld_logp=0,
+                  slots=None, vertex_slots=None):
+    """mode 5: n rows of T ids (and their log-probabilities, or None) -> vertices i32 [n, V, 2], polygon records i32 [n x P, 16], sums
+    f32 [n x P], counters i32 [n, 4]; the class table is FlorenceProcessor.poly_class_table's"""
+    P, V = poly_slots(T)
+    return L.make_op(L.OP_REGION_OCR, L.F32, p=[ids_ptr, table_ptr, logp_ptr, verts_ptr, rec_ptr, sum_ptr, rows_ptr, cells_ptr],
+                     i={0: L.OCR_MODE_POLYS, 1: n, 2: T, 3: P if slots is None else slots, 4: table_len, 5: ld_ids, 6: ld_logp, 7: R, 8: eos,
+                        9: V if vertex_slots is None else vertex_slots})
+
+
+def poly_mask_op(rec_ptr, rows_ptr, verts_ptr, cells_ptr, mask_ptr, count_ptr, n, T, instances, H, W, R):
+    """mode 6: mode 5's records, counters and vertices of n rows of T tokens -> tile-local bit masks u32 [n, instances, R, (R + 31) / 32]
+    and set bits per pixel row i32 [n, instances, R], clipped to the H x W frame"""
+    return L.make_op(L.OP_REGION_OCR, L.F32, p=[rec_ptr, rows_ptr, verts_ptr, None, mask_ptr, count_ptr, None, cells_ptr],
+                     i={0: L.OCR_MODE_MASKS, 1: n, 2: T, 3: instances, 4: H, 5: W, 7: R})
+
+
 def ocr_cells(origins, R: int):
     """The cells table of mode 1 for tiles of R x R pixels at `origins` [(x, y)] (a grid: every x with every y), one row per tile:
     [origin x, origin y, lo x, hi x, lo y, hi y].  Per axis the boundary between neighbouring tiles is the midpoint of their overlap,
@@ -2401,6 +2424,71 @@ class Florence2Captioner:
             out = self.decode_tiles(image_u8, origins, [prompts[p] for p in prompt_index], max_new_tokens, controls, parse=parse,
                                     fetch={"records": rec[:, :M], "sums": sums[:, :M], "rows": rows})
         out.origins, out.prompt_index, out.tile_index = origins, prompt_index, tile_index
+        return out
+
+    # ---- polygon answers and bit masks over tiles (OMNI_OP_REGION_OCR modes 0, 5 and 6)
+    @torch.inference_mode()
+    def segment_regions(self, image_u8: torch.Tensor, origins, prompts, class_table, max_new_tokens=256, instances=4, masks=True,
+                        controls=None, cells=None):
+        """Polygon answers and their masks for windows of a screenshot: `decode_tiles` rows (origin, prompt) whose prompts are those of
+        <REFERRING_EXPRESSION_SEGMENTATION> or <REGION_TO_SEGMENTATION> (`FlorenceProcessor.segment_prompt_ids`).  Behind the last step
+        of every chunk OMNI_OP_REGION_OCR mode 5 parses the chunk's ids and log-probabilities into polygons on the device and, with
+        `masks`, mode 6 rasters the first `instances` instances of every row into tile-local bit masks from mode 5's outputs where they
+        lie.  One read-back at the end.  class_table: `FlorenceProcessor.poly_class_table()`.  cells: per row [origin x, origin y, lo x,
+        hi x, lo y, hi y], the cell whose instances the row keeps (as `ocr_cells` writes them; the origins must be the row's); None =
+        `ocr_cells(origins, R)`, the grid the given origins span — right when the rows are every tile of a frame's grid, while rows put
+        to single tiles on purpose want cells without ends (-2^31, OCR_INF).
+        Returns `decode_tiles`' object with `origins`, `vertices` i32 [rows, V, 2], `records` i32 [rows, P, 16], `sums` f32 [rows, P],
+        `rows` i32 [rows, 4] and, with `masks`, `masks` i32 [rows, instances, R, (R + 31) // 32] (the bits of u32 words) and `counts` i32
+        [rows, instances, R] (T = max_new_tokens + 1; P, V = poly_slots(T)) — the op's outputs as include/omni_amd.h describes them.
+        ValueError before anything reaches the device: `decode_tiles`' own, no class table, max_new_tokens below 2, `instances` outside
+        1..64, cells that are not one row of six 32-bit integers per origin starting with that origin."""
+        R = int(self.resolution)
+        if class_table is None:
+            raise ValueError("segment_regions needs class_table (FlorenceProcessor.poly_class_table())")
+        table = check_class_table(class_table)
+        if isinstance(instances, bool) or not isinstance(instances, int) or not 1 <= instances <= 64:
+            raise ValueError(f"instances must be an integer in 1..64 (mask slots per row), got {instances!r}")
+        prompts, _ = self._check_frame_rows(image_u8, prompts, max_new_tokens, controls)
+        if max_new_tokens < 2:
+            raise ValueError("max_new_tokens must be at least 2: a polygon answer has no room in one token")
+        self.prompt_batch(prompts, R)                      # (an id outside the token table)
+        origins = [(int(x), int(y)) for x, y in origins]
+        if len(origins) != len(prompts):
+            raise ValueError(f"{len(origins)} origins for {len(prompts)} prompts: one prompt per origin is needed")
+        if any(abs(v) > 2 ** 30 for o in origins for v in o):
+            raise ValueError("origins must lie within +-2^30")
+        cell_rows = ocr_cells(origins, R) if cells is None else [[int(v) for v in c] for c in cells]
+        if len(cell_rows) != len(origins) or any(len(c) != 6 or (c[0], c[1]) != o or not all(-2 ** 31 <= v <= OCR_INF for v in c)
+                                                 for c, o in zip(cell_rows, origins)):
+            raise ValueError("cells must hold one row [origin x, origin y, lo x, hi x, lo y, hi y] of 32-bit integers per origin")
+        H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
+        n_all, T, I, WR = len(origins), max_new_tokens + 1, int(instances), (R + 31) // 32
+        P, V = poly_slots(T)
+        dev = self.device
+        with self._lock:
+            with torch.cuda.stream(self.stream):
+                cells = torch.tensor(cell_rows, dtype=torch.int32).to(dev, non_blocking=True)
+                tab = table.to(dev, non_blocking=True)
+                verts = torch.zeros((n_all, V, 2), dtype=torch.int32, device=dev)
+                rec = torch.zeros((n_all, P, 16), dtype=torch.int32, device=dev)
+                sums = torch.zeros((n_all, P), dtype=torch.float32, device=dev)
+                rows = torch.zeros((n_all, 4), dtype=torch.int32, device=dev)
+                fetch = {"vertices": verts, "records": rec, "sums": sums, "rows": rows}
+                if masks:
+                    fetch["masks"] = torch.zeros((n_all, I, R, WR), dtype=torch.int32, device=dev)
+                    fetch["counts"] = torch.zeros((n_all, I, R), dtype=torch.int32, device=dev)
+
+            def parse(s, n, cp):
+                L.launch(poly_parse_op(cp.ids.data_ptr(), tab.data_ptr(), cp.logp.data_ptr() + 4, cells[s:s + n].data_ptr(), verts[s:s + n].data_ptr(),
+                                       rec[s:s + n].data_ptr(), sums[s:s + n].data_ptr(), rows[s:s + n].data_ptr(), n, T, tab.numel(), R,
+                                       int(self.w.eos), ld_ids=T, ld_logp=T), self.stream)
+                if masks:
+                    L.launch(poly_mask_op(rec[s:s + n].data_ptr(), rows[s:s + n].data_ptr(), verts[s:s + n].data_ptr(), cells[s:s + n].data_ptr(),
+                                          fetch["masks"][s:s + n].data_ptr(), fetch["counts"][s:s + n].data_ptr(), n, T, I, H, W, R), self.stream)
+
+            out = self.decode_tiles(image_u8, origins, prompts, max_new_tokens, controls, parse=parse, fetch=fetch)
+        out.origins = origins
         return out
 
     # ---- teacher-forced scoring of given texts (OMNI_OP_GREEDY_STEP p5)

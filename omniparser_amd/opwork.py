@@ -71,10 +71,16 @@ def op_work(op, esz=4):
         if i[0] == 1:                               # queries and gallery once (a perfectly cached execution), the partials out
             return 2 * m * n * D, 4 * (m + n) * D + 8 * m * splits * kk
         return 0, 8 * m * splits * kk + 8 * m * kk
-    if k == 29:                                     # i0: 0 = tile cut (u8 window in, normalised pixels out), 1 = region parse, 3 = box parse
-        if i[0] == 0:
+    if k == 29:                                     # i0: 0 = tile cut (u8 window in, normalised pixels out), 1 = region parse, 3 = box parse,
+        if i[0] == 0:                               # 5 = polygon parse, 6 = mask raster
             n, R, ldo = i[1], i[4], i[13]
             return 2 * 3 * n * R * R, n * R * R * (3 + ldo * esz)
+        if i[0] == 5:                               # as the parses, plus the vertex slots: a record and a sum per polygon slot, 8 bytes per vertex
+            n, T, P, V = i[1], i[2], i[3], i[9]
+            return 0, n * (4 * T + (4 * (T - 1) if op.p[2] else 0) + 68 * P + 8 * V + 16 + 24)
+        if i[0] == 6:                               # records, rows, vertices and origins in (once: the blocks of a row share them in cache),
+            n, T, I, R = i[1], i[2], i[3], i[7]     # mask words and counts out; no flops: the edge tests are 64-bit integer work
+            return 0, n * (64 * (T // 2) + 8 * ((T - 1) // 2) + 16 + 24 + I * R * (4 * ((R + 31) // 32) + 4))
         n, T, M = i[1], i[2], i[3]                  # ids and log-probabilities in, records, sums and row counters out (class table: cached)
         slot = 72 if i[0] == 3 else 68              # a record of 16 ints and one sum (boxes: two)
         return 0, n * (4 * T + (4 * (T - 1) if op.p[2] else 0) + slot * M + 16 + 24)
@@ -100,7 +106,9 @@ def op_shape(op):
         return (i[10], i[9], i[7] if i[7] > 0 else i[8])
     if k == 28:                                     # embed: (crops, D, 0); match: (queries, D, gallery rows)
         return (i[1], i[3], 0 if i[0] == 0 else i[2])
-    if k == 29:                                     # cut: (tiles, R, 0); parse and boxes: (rows, T, 0)
+    if k == 29:                                     # cut: (tiles, R, 0); parse, boxes and polygons: (rows, T, 0); masks: (rows, R, instance slots)
+        if i[0] == 6:
+            return (i[1], i[7], i[3])
         return (i[1], i[4] if i[0] == 0 else i[2], 0)
     return (i[0], i[3], 0)
 
@@ -122,5 +130,6 @@ def op_kernel(op):
     if op.kind == 28:
         return ("visual_match (embed)", "visual_match (partial top-k)", "visual_match (merge)")[op.i[0]] if 0 <= op.i[0] <= 2 else "visual_match"
     if op.kind == 29:
-        return {0: "region_ocr (tile cut)", 1: "region_ocr (parse)", 3: "region_ocr (boxes)"}.get(op.i[0], "region_ocr")
+        return {0: "region_ocr (tile cut)", 1: "region_ocr (parse)", 3: "region_ocr (boxes)", 5: "region_ocr (polygons)",
+                6: "region_ocr (masks)"}.get(op.i[0], "region_ocr")
     return NAMES.get(op.kind, str(op.kind))

@@ -308,6 +308,11 @@ class ScreenParser:
         without text), [{"label", "query", "bbox", "confidence", "tile", "phrase"}]"""
         return U.locate(frame, {"model": self.cap, "processor": self.proc}, task=task, text=phrases, **kw)
 
+    def segment(self, frame: torch.Tensor, phrases=None, regions=None, **kw):
+        """`util.utils.segment` for a frame already on the device: polygons, masks and click points for every phrase, or for every box
+        of `regions` (frame pixels); exactly one of the two"""
+        return U.segment(frame, {"model": self.cap, "processor": self.proc}, text=phrases, regions=regions, **kw)
+
     def track(self, prev_frame: torch.Tensor, prev_elements, frame: torch.Tensor, elements, min_score=0.9):
         """`util.utils.track_elements` of two frames already on the device: [(prev_index, index, score)], the one-to-one mutual
         best matches between the elements of the previous frame and of this one"""

@@ -11,6 +11,9 @@ unchanged — plus what a GPU service needs and the reference lacks (SURVEY §8(
   latency};
 * `POST /locate/ {base64_image, phrases, task?}` -> {boxes, latency}: where the phrases are, in frame pixels, from the caption
   model's box tasks over tiles (`util.utils.locate`); a bad request (unknown task, no phrase, no tokenizer) is a 422;
+* `POST /segment/ {base64_image, phrases? | regions?}` -> {segments, latency}: the shapes of the phrases, or of what the boxes
+  `regions` (frame pixels) hold, from the caption model's segmentation tasks (`util.utils.segment`): polygons, bbox, area, a click
+  point on the shape and the confidence; masks do not travel.  A bad request (both or neither input, no tokenizer) is a 422;
 * OCR is not part of the hot path: a request may carry `ocr: {"texts": [...], "boxes": [[x0,y0,x1,y1] px]}`
   per image (never stored on the shared parser — requests are concurrent).
 """
@@ -54,6 +57,12 @@ class ParseService:
         start = time.time()
         boxes = self.parser.locate(base64_image, phrases, **({"task": task} if task else {}))
         return {"boxes": boxes, "latency": time.time() - start}
+
+    def segment_one(self, base64_image: str, phrases=None, regions=None) -> dict:
+        start = time.time()
+        found = self.parser.segment(base64_image, phrases, regions, return_masks=False)
+        keep = ("query", "region", "index", "polygons", "bbox", "area", "point", "confidence", "tile")
+        return {"segments": [{k: g[k] for k in keep if k in g} for g in found], "latency": time.time() - start}
 
     # ---- batch: device batching for equal-sized frames
     def screen_parser(self):
@@ -144,6 +153,11 @@ def build_app(config, service: Optional[ParseService] = None):
         phrases: Optional[List[str]] = None
         task: Optional[str] = None
 
+    class SegmentRequest(BaseModel):
+        base64_image: str
+        phrases: Optional[List[str]] = None
+        regions: Optional[List[List[float]]] = None
+
     @app.post("/parse/")
     def parse(req: ParseRequest):
         try:
@@ -162,6 +176,13 @@ def build_app(config, service: Optional[ParseService] = None):
     def locate(req: LocateRequest):
         try:
             return svc.locate_one(req.base64_image, req.phrases, req.task)
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+
+    @app.post("/segment/")
+    def segment(req: SegmentRequest):
+        try:
+            return svc.segment_one(req.base64_image, req.phrases, req.regions)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 

@@ -177,6 +177,12 @@ class Omniparser(object):
         generation, return_stats)."""
         return U.locate(np.asarray(decode_image(image_base64).convert("RGB")), self.caption_model_processor, text=phrases, **kw)
 
+    def segment(self, image_base64: str, phrases=None, regions=None, **kw):
+        """`utils.segment` of the screenshot: the shape of `phrases` (a phrase or a list) or of what the boxes `regions` (frame
+        pixels) hold — polygons, bit masks and a click point that lies on the shape, from the caption model alone.  kw:
+        `utils.segment`'s (max_new_tokens, overlap, min_confidence, instances, return_masks, generation, return_stats)."""
+        return U.segment(np.asarray(decode_image(image_base64).convert("RGB")), self.caption_model_processor, text=phrases, regions=regions, **kw)
+
     def find_similar(self, image_base64: str, exemplars_base64, top_k=5):
         """`parse`, then `utils.match_elements` of the parsed elements against exemplar images (base64, as the screenshot is):
         (parsed_content_list, per exemplar the top_k elements as {"index", "score"} by descending cosine similarity of the caption

@@ -75,6 +75,10 @@ TASK_PROMPTS_WITH_INPUT = {
     "<REGION_TO_DESCRIPTION>": "What does the region {input} describe?",
     "<REGION_TO_OCR>": "What text is in the region {input}?",
 }
+SEGMENT_PROMPTS = {                                     # the two tasks that answer in polygons: `segment_prompt_ids`, `segment`
+    "<REFERRING_EXPRESSION_SEGMENTATION>": "Locate {input} in the image with mask",
+    "<REGION_TO_SEGMENTATION>": "What is the polygon mask of region {input}",
+}
 TASKS_WITH_REGION = ("<REGION_TO_CATEGORY>", "<REGION_TO_DESCRIPTION>", "<REGION_TO_OCR>")
 TASKS_WITH_INPUT = ("<CAPTION_TO_PHRASE_GROUNDING>", "<REFERRING_EXPRESSION_SEGMENTATION>", "<REGION_TO_SEGMENTATION>",
                     "<OPEN_VOCABULARY_DETECTION>", "<REGION_TO_CATEGORY>", "<REGION_TO_DESCRIPTION>", "<REGION_TO_OCR>")
@@ -220,6 +224,47 @@ class FlorenceProcessor:
                 table[t] = L.OCR_CLASS_TEXT
         self._loc = (table, texts)
         return self._loc
+
+    def poly_class_table(self):
+        """(class table u16 [vocab], per-token texts) for OMNI_OP_REGION_OCR mode 5 and `parse_polygon_answer`: `loc_class_table`'s
+        with `<sep>`, `<poly>` and `</poly>` re-classed L.OCR_CLASS_SEP / _POLY / _POLY_END (there they are HARD: they hold '<'), the same
+        texts.  ValueError naming the tokenizer file when one of the three is missing."""
+        if getattr(self, "_poly", None) is not None:
+            return self._poly
+        table, texts = self.loc_class_table()
+        table = table.copy()
+        for tok, c in (("<sep>", L.OCR_CLASS_SEP), ("<poly>", L.OCR_CLASS_POLY), ("</poly>", L.OCR_CLASS_POLY_END)):
+            t = self.tok.token_to_id(tok)
+            if t is None or not 0 <= t < len(table):
+                raise ValueError(f"{Path(self.model_dir) / 'tokenizer.json'}: the polygon token {tok} is missing (the tokenizer of a Florence-2 "
+                                 "checkpoint has <sep>, <poly> and </poly>)")
+            table[t] = c
+        self._poly = (table, texts)
+        return self._poly
+
+    def segment_prompt_ids(self, task, text=None, region=None, size=None):
+        """token ids (bos ... eos) of the prompt of a segmentation task, the sentence transformers' `_construct_prompts` builds:
+        <REFERRING_EXPRESSION_SEGMENTATION> takes `text`, <REGION_TO_SEGMENTATION> a `region` [x0, y0, x1, y1] in pixels of an image of
+        `size` (width, height), written as the four location tokens `quantize_box` gives.  ValueError: another task, the wrong kind of
+        input, no tokenizer.  (`task_prompt_ids` keeps refusing both tasks: their answers need `segment`, not `locate`.)"""
+        if task not in SEGMENT_PROMPTS:
+            raise ValueError(f"task {task!r} is not a segmentation task ({', '.join(SEGMENT_PROMPTS)})")
+        if task == "<REGION_TO_SEGMENTATION>":
+            if text is not None or region is None or size is None:
+                raise ValueError(f"task {task} takes a region (box in pixels) and the size of its image, no text")
+            box = [float(v) for v in region]
+            if len(box) != 4 or len(tuple(size)) != 2 or min(size) <= 0:
+                raise ValueError("a region is [x0, y0, x1, y1] in pixels of an image of size (width, height)")
+            given = "".join(f"<loc_{b}>" for b in self.quantize_box(box, size))
+        else:
+            if not isinstance(text, str) or region is not None:
+                raise ValueError(f"task {task} takes a text, no region")
+            given = text.replace(task, "").strip()
+        sentence = SEGMENT_PROMPTS[task].format(input=given)
+        if self.tok is None:
+            where = Path(self.model_dir) / "tokenizer.json" if self.model_dir is not None else "tokenizer.json (no model directory was given)"
+            raise ValueError(f"the prompt {sentence!r} needs a tokenizer: {where} is missing")
+        return [self.bos_id] + list(self.tok.encode(sentence, add_special_tokens=False).ids) + [self.eos_id]
 
     def batch_decode(self, ids, skip_special_tokens=True):
         special = self.special
@@ -816,6 +861,69 @@ def parse_box_answer(ids_row, processor, size, grammar):
     return out
 
 
+_POLY_RUN = r"(?:(?:<loc_\d+>|<sep>|<poly>|</poly>){4,})"
+_POLY_PHRASE = r"^\s*(.*?)(?=<od>|</od>|<box>|</box>|<bbox>|</bbox>|<loc_|<poly>)"
+
+
+def parse_polygon_answer(ids_row, processor, size):
+    """The answer of ONE image to a segmentation task parsed on the host FROM ITS TEXT, as transformers' Florence2PostProcessor parses
+    it for the "polygons" type (parse_description_with_polygons_from_text_and_spans with allow_empty_phrase, no box at the start).  The
+    device parses tokens instead (OMNI_OP_REGION_OCR mode 5) and flags the rows in which that can differ; this is what those rows
+    fall back to.  ids_row, size: as in `parse_ocr_regions`.
+    -> one entry per instance, in the answer's order: {"polygons": [[x0, y0, x1, y1, ...], ...] in pixels of the image (a polygon may
+    be empty), "columns": the columns of `ids_row` whose location tokens made vertices}"""
+    import re
+    text, owner = _answer_text(ids_row, processor)
+    w, h = size
+    out = []
+    for m in re.finditer(_POLY_RUN, text):
+        phrase = m.group(0)
+        if not re.search(_POLY_PHRASE, re.sub(r"^<loc_\d+>", "", phrase, count=1)):
+            continue
+        if "<poly>" in phrase and "</poly>" in phrase:
+            contents = [(m.start() + q.start(1), q.group(1)) for q in re.finditer(r"<poly>(.*?)</poly>", phrase)]
+        else:
+            contents = [(m.start(), phrase)]
+        for at, content in contents:
+            found = list(re.finditer(r"((?:<loc_\d+>)+)(?:<sep>|$)", content))
+            if not found:
+                continue
+            polygons, columns = [], []
+            for q in found:
+                bins = list(re.finditer(r"<loc_(\d+)>", q.group(1)))
+                bins = bins[:len(bins) - len(bins) % 2]
+                polygons.append([dequantize_bin(int(b.group(1)), h if k & 1 else w) for k, b in enumerate(bins)])
+                columns += [owner[at + q.start(1) + b.start()] for b in bins]
+            out.append({"polygons": polygons, "columns": columns})
+    return out
+
+
+def raster_polygons(polygons, origin, size, frame=None):
+    """The mask rule of OMNI_OP_REGION_OCR mode 6 on the host (for instances beyond the device's instance slots and for fallback
+    rows): bool [h, w] (y, x) of a window of `size` = (w, h) pixels whose top-left pixel is `origin` = (x, y) in the coordinates of
+    `polygons` ([[x0, y0, x1, y1, ...], ...]).  A pixel is set when its centre lies inside at least one polygon of three or more
+    vertices, even-odd per polygon, in exact integer arithmetic on doubled coordinates; with `frame` = (W, H) pixels outside
+    [0, W) x [0, H) stay clear."""
+    w, h = size
+    ox, oy = origin
+    px = (2 * (np.arange(w, dtype=np.int64) + ox) + 1)[None, :]
+    py = (2 * (np.arange(h, dtype=np.int64) + oy) + 1)[:, None]
+    out = np.zeros((h, w), bool)
+    for poly in polygons:
+        pts = [(2 * int(poly[k]), 2 * int(poly[k + 1])) for k in range(0, len(poly) - 1, 2)]
+        if len(pts) < 3:
+            continue
+        par = np.zeros((h, w), bool)
+        for k, (bx, by) in enumerate(pts):
+            ax, ay = pts[k - 1]
+            lhs, rhs = (px - ax) * (by - ay), (py - ay) * (bx - ax)
+            par ^= ((ay > py) != (by > py)) & ((lhs < rhs) if by > ay else (lhs > rhs))
+        out |= par
+    if frame is not None:
+        out &= (((py - 1) // 2 >= 0) & ((py - 1) // 2 < frame[1])) & (((px - 1) // 2 >= 0) & ((px - 1) // 2 < frame[0]))
+    return out
+
+
 def _box_tasks_check(task, text):
     """(grammar, queries): the phrases a box task is asked with, [None] for the tasks without an input"""
     if task not in _BOX_TASKS:
@@ -971,6 +1079,164 @@ def describe_regions(image_source, boxes_px, caption_model_processor, task="<REG
         prompts.append(processor.task_prompt_ids(task, region=region, size=(R, R)))
     out = model.decode_tiles(_frame_on(image_source, model.device), origins, prompts, max_new_tokens, controls=generation)
     return [t.strip() for t in processor.batch_decode(out.ids, skip_special_tokens=True)]
+
+
+def _mask_point(mask, origin):
+    """[x, y] of the set pixel nearest the centroid of the set pixels of a bool mask whose top-left pixel is `origin` (ties: the lower
+    y, then the lower x; exact: distances are compared as integers scaled by the pixel count), None for an empty mask"""
+    ys, xs = np.nonzero(mask)
+    if not len(xs):
+        return None
+    n = len(xs)
+    d = (n * xs.astype(np.int64) - int(xs.sum())) ** 2 + (n * ys.astype(np.int64) - int(ys.sum())) ** 2
+    k = int(np.argmin(d))                                  # the first of the equals: np.nonzero lists pixels by ascending y, then x
+    return [int(xs[k]) + origin[0], int(ys[k]) + origin[1]]
+
+
+@torch.inference_mode()
+def segment(image_source, caption_model_processor, text=None, regions=None, max_new_tokens=256, overlap=128, min_confidence=0.0, instances=4,
+            return_masks=True, generation=None, return_stats=False):
+    """What shape is it?  Polygons and pixel masks in frame pixels from the caption model's two segmentation tasks —
+    `Florence2Captioner.segment_regions`: rows over native-resolution tiles of the frame, decoded greedily, the polygon answers parsed
+    and rastered on the device.  Exactly one of:
+    text: a phrase or a list of phrases, <REFERRING_EXPRESSION_SEGMENTATION>; every phrase is put to every tile of
+      `ScreenParser.tile_origins(W, H, R, R, overlap)`, and an instance seen by two overlapping tiles is returned by the tile whose cell
+      holds the centre of its bounding box (`florence.ocr_cells`), as in `locate`;
+    regions: boxes [x0, y0, x1, y1] in frame pixels, <REGION_TO_SEGMENTATION>; each box goes to the tile whose cell holds its centre,
+      clipped to that tile and quantised in tile coordinates exactly as `describe_regions` does.  Every instance of the answer is
+      returned: a box was put to ONE tile, so there is nothing to de-duplicate, and what a box gives does not depend on the other
+      boxes of the call.
+    -> [{"query" (the phrase) or "region" (the box), "index" (its ordinal in the input), "polygons" [[x0, y0, x1, y1, ...], ...],
+    "bbox" [x0, y0, x1, y1] over all vertices, "area" (set pixels), "confidence", "tile", "point", "mask", "mask_origin"}], input by
+    input, tile by tile, in the answer's order within a row.  mask: a bool array [bbox height, bbox width] whose top-left pixel is
+    mask_origin = (bbox x0, bbox y0): a pixel is set when it lies in the frame and in its tile and its centre lies inside a polygon of
+    three or more vertices of the instance (even-odd per polygon) — empty, [0, w] or [h, 0], for an instance whose vertices share
+    an x or a y; None with return_masks=False.  point: [x, y] of the set pixel
+    nearest the centroid of the set pixels (ties: the lower y, then the lower x) — a click point that lies ON the element; None for
+    an empty mask.  confidence = exp(mean log-probability of the instance's vertex tokens); instances below `min_confidence` are
+    dropped.  The first `instances` instances of a row are rastered on the device, later ones by `raster_polygons`; rows the device
+    flags as holding a token it does not parse are re-parsed from their text by `parse_polygon_answer` and rastered on the host.
+    return_stats=True: (instances, per row {"index", "tile", "polygons", "found", "kept", "truncated", "fallback"}).
+    ValueError before anything reaches the model: both or neither of text and regions, an empty or non-string phrase, a box that is
+    not four numbers with x0 <= x1 and y0 <= y1, no tokenizer.json or one without <sep> / <poly> / </poly>, min_confidence outside
+    0..1, instances outside 1..64, overlap outside 0..R-1, and `segment_regions`' own."""
+    import math
+    from ..florence import ocr_cells
+    from ..pipeline import ScreenParser
+    model, processor = caption_model_processor["model"], caption_model_processor["processor"]
+    if (text is None) == (regions is None):
+        raise ValueError("segment takes exactly one of text (a phrase or a list of phrases) and regions (boxes in frame pixels)")
+    if isinstance(min_confidence, bool) or not isinstance(min_confidence, (int, float)) or not 0.0 <= min_confidence <= 1.0:
+        raise ValueError(f"min_confidence must be a number in 0..1, got {min_confidence!r}")
+    if isinstance(instances, bool) or not isinstance(instances, int) or not 1 <= instances <= 64:
+        raise ValueError(f"instances must be an integer in 1..64, got {instances!r}")
+    R = int(model.resolution)
+    if isinstance(overlap, bool) or not isinstance(overlap, int) or not 0 <= overlap < R:
+        raise ValueError(f"overlap must be an integer in 0..{R - 1} (tiles are {R} x {R}), got {overlap!r}")
+    if text is not None:
+        queries = [text] if isinstance(text, str) else list(text)
+        if not queries or not all(isinstance(q, str) and q.strip() for q in queries):
+            raise ValueError("<REFERRING_EXPRESSION_SEGMENTATION> needs a phrase or a list of phrases")
+    else:
+        queries = [[float(v) for v in b] for b in regions]
+        if any(len(b) != 4 or not (b[0] <= b[2] and b[1] <= b[3]) for b in queries):
+            raise ValueError("a region is [x0, y0, x1, y1] in frame pixels with x0 <= x1 and y0 <= y1")
+    table, _texts = processor.poly_class_table()
+    if isinstance(image_source, str):
+        image_source = Image.open(image_source)
+    if isinstance(image_source, Image.Image):
+        image_source = np.asarray(image_source.convert("RGB"))
+    H, W = int(image_source.shape[0]), int(image_source.shape[1])
+    tiles = ScreenParser.tile_origins(W, H, R, R, overlap)[0]
+    grid = ocr_cells(tiles, R)
+    origins, prompts, index, tile_of = [], [], [], []
+    if text is not None:
+        for i, q in enumerate(queries):
+            row = processor.segment_prompt_ids("<REFERRING_EXPRESSION_SEGMENTATION>", text=q)
+            for k, o in enumerate(tiles):
+                origins.append(o)
+                prompts.append(row)
+                index.append(i)
+                tile_of.append(k)
+    else:
+        for i, b in enumerate(queries):
+            k = next(k for k, c in enumerate(grid) if _owns(c, [b[0], b[1], b[2], b[3]]))     # the cells partition the plane
+            ox, oy = tiles[k]
+            region = [min(max(b[0] - ox, 0), R), min(max(b[1] - oy, 0), R), min(max(b[2] - ox, 0), R), min(max(b[3] - oy, 0), R)]
+            origins.append((ox, oy))
+            prompts.append(processor.segment_prompt_ids("<REGION_TO_SEGMENTATION>", region=region, size=(R, R)))
+            index.append(i)
+            tile_of.append(k)
+    if not origins:
+        return ([], []) if return_stats else []
+    # phrases: the cells of the frame's tile grid; regions: every row owns the whole plane
+    cells = ocr_cells(origins, R) if text is not None else [[ox, oy, -2 ** 31, 2 ** 31 - 1, -2 ** 31, 2 ** 31 - 1] for ox, oy in origins]
+    out = model.segment_regions(_frame_on(image_source, model.device), origins, prompts, table, max_new_tokens=max_new_tokens, instances=instances,
+                                masks=True, controls=generation, cells=cells)
+    records, vertices, sums = np.asarray(out.records), np.asarray(out.vertices), np.asarray(out.sums)
+    words = np.asarray(out.masks).view(np.uint32)
+    key = "query" if text is not None else "region"
+    found_instances, stats = [], []
+    for r, (ox, oy) in enumerate(origins):
+        n_poly, n_inst, flags, kept = (int(v) for v in out.rows[r, :4])
+        cands = []                                          # (polygons in frame pixels, log-probability sum, tokens, device slot or None)
+        if flags & 1:                                       # from the text, on the host
+            ids = out.ids[r].tolist()
+            for g in parse_polygon_answer(ids, processor, (R, R)):
+                polys = [[v + (oy if q & 1 else ox) for q, v in enumerate(p)] for p in g["polygons"]]
+                cands.append((polys, float(sum(float(out.logp[r, j - 1]) for j in g["columns"])), len(g["columns"]), None))
+            n_poly, n_inst = sum(len(c[0]) for c in cands), len(cands)
+        else:
+            for k in range(n_poly):
+                rec = records[r, k]
+                if rec[2] == 0:
+                    cands.append(([], 0.0, 0, int(rec[1]) if rec[1] < instances else None))
+                c = cands[-1]
+                cands[-1] = (c[0] + [vertices[r, rec[3]:rec[3] + rec[4]].reshape(-1).tolist()], c[1] + float(sums[r, k]), c[2] + 2 * int(rec[4]), c[3])
+        kept = 0
+        for polys, total, count, slot in cands:
+            xs, ys = [v for p in polys for v in p[0::2]], [v for p in polys for v in p[1::2]]
+            if not xs or not _owns(cells[r], [min(xs), min(ys), max(xs), max(ys)]):
+                continue
+            kept += 1
+            conf = math.exp(total / count)
+            if conf < min_confidence:
+                continue
+            bbox = [min(xs), min(ys), max(xs), max(ys)]
+            w, h = bbox[2] - bbox[0], bbox[3] - bbox[1]
+            if slot is not None:                            # the device's tile-local bits: only the box's pixel rows and words are unpacked
+                x0, x1 = bbox[0] - ox, bbox[2] - ox
+                w0, w1 = x0 // 32, (x1 + 31) // 32
+                part = words[r, slot, bbox[1] - oy:bbox[3] - oy, w0:w1]
+                bits = ((part[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(h, 32 * (w1 - w0))
+                mask = np.ascontiguousarray(bits[:, x0 - 32 * w0:x1 - 32 * w0])
+            else:
+                mask = raster_polygons(polys, (bbox[0], bbox[1]), (w, h), frame=(W, H))
+                mask &= raster_polygons([[ox, oy, ox + R, oy, ox + R, oy + R, ox, oy + R]], (bbox[0], bbox[1]), (w, h))    # tile pixels only
+            found_instances.append({key: queries[index[r]], "index": index[r], "polygons": polys, "bbox": bbox, "area": int(mask.sum()),
+                                    "confidence": conf, "tile": tile_of[r], "point": _mask_point(mask, (bbox[0], bbox[1])),
+                                    "mask": mask if return_masks else None, "mask_origin": (bbox[0], bbox[1])})
+        stats.append({"index": index[r], "tile": tile_of[r], "polygons": n_poly, "found": n_inst, "kept": kept, "truncated": bool(flags & 2),
+                      "fallback": bool(flags & 1)})
+    return (found_instances, stats) if return_stats else found_instances
+
+
+def segment_elements(image_source, elements, caption_model_processor, **kw):
+    """The shape of every parsed element: `segment(regions=...)` with the elements' boxes (a `parsed_content_list` with ratio bboxes)
+    -> per element the most confident instance its box gave, or None when it gave none."""
+    if kw.get("return_stats") or "text" in kw or "regions" in kw:
+        raise ValueError("segment_elements takes the regions from the elements and returns instances only")
+    if isinstance(image_source, str):
+        image_source = Image.open(image_source)
+    if isinstance(image_source, Image.Image):
+        image_source = np.asarray(image_source.convert("RGB"))
+    H, W = image_source.shape[0], image_source.shape[1]
+    boxes = [[e["bbox"][0] * W, e["bbox"][1] * H, e["bbox"][2] * W, e["bbox"][3] * H] for e in elements]
+    best = [None] * len(boxes)
+    for g in segment(image_source, caption_model_processor, regions=boxes, **kw):
+        if best[g["index"]] is None or g["confidence"] > best[g["index"]]["confidence"]:
+            best[g["index"]] = g
+    return best
 
 
 @torch.inference_mode()
